@@ -13,6 +13,11 @@ pair shard, deterministic gradient reduction, RCCL all-reduce of the flat
 gradient (N > 1), TF-form Adam.  Inputs (packed pair records) are resident in
 HBM before timing starts.  Prints ONE JSON line (rank 0).
 
+A plain run sets up, warms up, times the K steps and prints the line.  --full adds, outside
+the timed steps, everything else the line can report (CPU baseline, preparation times,
+kernel event time and roofline, forward-only rate); --dump-outputs DIR writes the arrays
+the last timed step left (params, grad, adam_m, adam_v, loss) as DIR/<name>.npy.
+
   python bench.py [--gpus N --steps K --warmup W]   (N > 1: starts N ranks itself)
   torchrun --nproc-per-node N bench.py --gpus N ...  (--gpus must equal WORLD_SIZE)
 """
@@ -43,8 +48,16 @@ def parse():
     p.add_argument('--dropout', type=float, default=0.1)
     p.add_argument('--records', choices=('f32', 'bf16'), default='f32',
                    help='storage of Â in the pair records (bf16 = config C3); math is fp32')
+    p.add_argument('--full', action='store_true',
+                   help='also measure what the headline figure does not need, outside the timed '
+                        'steps: the CPU baseline, the once-per-batch preparation (pack_ms, '
+                        'order_ms), the kernel event time behind the roofline figures, the '
+                        'forward-only rate.  Off: those fields are null')
+    p.add_argument('--dump-outputs', default='', metavar='DIR',
+                   help='write what the last timed step left its caller (params, grad, adam_m, '
+                        'adam_v, loss) as DIR/<name>.npy, float32')
     p.add_argument('--cpu-sample', type=int, default=0,
-                   help='pairs for the CPU baseline (0 = auto, -1 = skip)')
+                   help='--full: pairs for the CPU baseline (0 = auto, -1 = skip)')
     p.add_argument('--order', choices=('class', 'batch'), default='class',
                    help='record processing order: class-balanced (sg_pair_order) or batch order')
     p.add_argument('--chunk', type=int, default=4_000_000,
@@ -159,6 +172,21 @@ def time_preparation(model, gs, shard, batch, stream, args):
     return out
 
 
+def dump_outputs(model, out_dir):
+    """--dump-outputs: what the last timed step left its caller, one float32 .npy per array:
+    the updated parameters and Adam moments, the step's (reduced) gradient, and the loss it
+    evaluated as [loss_mse, regularisation].  A few thousand floats each; the inputs are
+    seeded, so two builds run with the same arguments can be compared array for array."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {'params': model.params, 'grad': model.grad, 'adam_m': model.adam_m,
+              'adam_v': model.adam_v,
+              'loss': model.torch.stack([model.loss_buf[0], model.reg_buf[0]])}
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + '.npy'),
+                t.detach().cpu().numpy().astype(np.float32))
+
+
 def launch_ranks(args) -> int:
     """`python bench.py --gpus N` without a torchrun environment: start the N ranks as
     children under torch.distributed.run (one process per GPU, 127.0.0.1 rendezvous)
@@ -190,6 +218,8 @@ def main():
         args.steps = 3 if web else 50
     if args.warmup is None:
         args.warmup = 1 if web else 10
+    if args.steps < 1 or args.warmup < 0:
+        sys.exit('bench.py: --steps must be >= 1 and --warmup >= 0')
     import numpy as np
     import torch
     import torch.distributed as dist
@@ -305,7 +335,7 @@ def main():
         model.workspace(shard.chunk if streamed else batch.n_pairs)
     stream = torch.cuda.current_stream()
     prep = time_preparation(model, gs, shard, batch, stream, args) \
-        if (not web and not streamed and args.source != 'store') else None
+        if (args.full and not web and not streamed and args.source != 'store') else None
     if streamed and shard.keep_orders and shard.uses_store(model):
         # the store-sourced chunks' batches and class orders, built once before the timed
         # steps and reused by every step (AllPairsStream.prepare), as the resident shard's
@@ -390,8 +420,10 @@ def main():
                   file=sys.stderr, flush=True)
     # the loss of the last timed step (before the event steps below move the parameters)
     loss = float(model.loss_buf[0].item() + model.reg_buf[0].item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(model, args.dump_outputs)
     event_steps = 0
-    if args.events == 'after':
+    if args.full and args.events == 'after':
         # the roofline's kernel time: HIP events around as many extra training steps right
         # after the timed region (they keep training: params, Adam state and step_count
         # advance by event_steps more; params_agree and loss above are the timed run's)
@@ -400,12 +432,13 @@ def main():
         torch.cuda.synchronize()
         event_steps = args.steps
 
-    kern_ms = float(np.mean([a.elapsed_time(b) for a, b in ev]))
+    # None: a plain run with --events after records no events (the roofline needs --full)
+    kern_ms = float(np.mean([a.elapsed_time(b) for a, b in ev])) if ev else None
     total_pairs = shard.total
     # the eval path (train.py:47-74 test matrix; pred_sim_without_act): forward only over
     # the same resident batch, one launch per pass (reported beside the training metric)
     fwd_rate = None
-    if world == 1 and batch is not None and not ew:
+    if args.full and world == 1 and batch is not None and not ew:
         torch.cuda.synchronize()
         f0 = time.perf_counter()
         for _ in range(5):
@@ -420,12 +453,13 @@ def main():
         flops_pair = gs.flops_per_pair_web() if web else gs.flops_per_pair(
             D=D, pool={'default': 'padding'}.get(args.stack, args.stack))
         bytes_pair = gs.csr_bytes_per_pair() if web else shard.record_bytes
-        kern_pairs_s = shard.n / (kern_ms * 1e-3)
+        kern_pairs_s = shard.n / (kern_ms * 1e-3) if kern_ms is not None else 0.0
         achieved_tf = kern_pairs_s * flops_pair / 1e12
         achieved_gbs = kern_pairs_s * bytes_pair / 1e9
         traffic, traffic_src = None, None
         tj = os.path.join(ROOT, 'profiles', 'traffic.json')
-        if model.kernel_path == 1 and args.records == 'f32' and os.path.isfile(tj) and \
+        if kern_ms is not None and model.kernel_path == 1 and args.records == 'f32' and \
+                os.path.isfile(tj) and \
                 args.stack == 'default' and args.source != 'store':
             with open(tj) as f:
                 t = json.load(f)
@@ -442,7 +476,7 @@ def main():
                 traffic_src = ('none: profiles/traffic.json ({}) was measured on other sg_fast '
                                'sources'.format(t.get('tree', '?')))
         cpu = None
-        if world == 1 and args.cpu_sample >= 0:
+        if args.full and world == 1 and args.cpu_sample >= 0:
             try:
                 if web:
                     sys.path.insert(0, os.path.join(ROOT, 'tests'))
@@ -520,7 +554,10 @@ def main():
                            'ncclAllReduce on the compute stream' if collective == 'rccl' else
                            'torch.distributed', 4 * (model.grad.numel() + 1))
                            if collective else None)},
-            'roofline': {'bound': 'mfma', 'achieved': achieved_tf, 'peak': FP32_PEAK_TFLOPS,
+            'full': args.full,
+            # null without kernel event times (--full, or --events timed)
+            'roofline': None if kern_ms is None else {
+                         'bound': 'mfma', 'achieved': achieved_tf, 'peak': FP32_PEAK_TFLOPS,
                          'unit': 'TFLOP/s', 'frac': achieved_tf / FP32_PEAK_TFLOPS,
                          'traffic': traffic, 'traffic_source': traffic_src,
                          'note': 'fp32 compute roof (gfx950 vector fp32 == f32 MFMA peak); '
@@ -535,7 +572,8 @@ def main():
                                      if args.events == 'timed' else
                                      'events on {} steps right after the timed region'.format(
                                          args.steps))},
-            'roofline_hbm': {'achieved': achieved_gbs, 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
+            'roofline_hbm': None if kern_ms is None else {
+                             'achieved': achieved_gbs, 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
                              'frac': achieved_gbs / HBM_PEAK_GBS,
                              'bytes_per_pair': bytes_pair},
             'cpu_baseline': cpu,

@@ -9,7 +9,7 @@ mkdir -p "$OUT"
 cd "$ROOT"
 run() {  # name, args...
   local name=$1; shift
-  timeout -k 10 300 python bench.py "$@" --json-out "$OUT/$name.json" > "$OUT/$name.log" 2>&1
+  timeout -k 10 300 python bench.py --full "$@" --json-out "$OUT/$name.json" > "$OUT/$name.log" 2>&1
   local rc=$?
   echo "$name rc=$rc"
   [ $rc -eq 0 ] || exit $rc

@@ -9,10 +9,10 @@ ROOT=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$ROOT/gpurun_out/$TAG
 mkdir -p "$OUT"
 cd "$ROOT"
-timeout -k 10 120 python bench.py --emulate-world $W --steps 200 --warmup 20 --cpu-sample -1 \
+timeout -k 10 120 python bench.py --full --emulate-world $W --steps 200 --warmup 20 --cpu-sample -1 \
   --json-out "$OUT/emu$W.json" > "$OUT/emu$W.log" 2>&1
 rc=$?; echo "emu$W rc=$rc"; [ $rc -eq 0 ] || exit $rc
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 200 rocprofv3 --kernel-trace -d "$OUT/trace" -o run --output-format csv -- \
-  python3 "$ROOT/bench.py" --emulate-world $W --steps 50 --warmup 5 --cpu-sample -1 > "$OUT/trace.log" 2>&1
+  python3 "$ROOT/bench.py" --full --emulate-world $W --steps 50 --warmup 5 --cpu-sample -1 > "$OUT/trace.log" 2>&1
 rc=$?; echo "trace rc=$rc"; exit $rc

@@ -10,7 +10,7 @@ mkdir -p "$OUT"
 cd "$ROOT"
 run() {  # name lib args...
   local n=$1 lib=$2; shift 2
-  SG_LIB=$lib timeout -k 10 300 python bench.py --cpu-sample -1 "$@" --json-out "$OUT/$n.json" > "$OUT/$n.log" 2>&1
+  SG_LIB=$lib timeout -k 10 300 python bench.py --full --cpu-sample -1 "$@" --json-out "$OUT/$n.json" > "$OUT/$n.log" 2>&1
   local r=$?
   [ $r -eq 0 ] || { echo "$n rc=$r"; tail -5 "$OUT/$n.log"; exit $r; }
   python -c "import json;d=json.load(open('$OUT/$n.json'));print('$n', round(d['value']/1e6,2),'M pairs/s', round(d['ms_per_step'],3),'ms')"

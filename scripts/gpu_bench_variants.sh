@@ -12,7 +12,7 @@ REPS=${REPS:-2}
 for rep in $(seq 1 $REPS); do
   for lib in "$@"; do
     n=$(basename "$lib" .so)
-    SG_LIB=$ROOT/$lib timeout -k 10 300 python bench.py --cpu-sample -1 --steps ${STEPS:-60} --warmup 10 ${BENCH_ARGS:-} \
+    SG_LIB=$ROOT/$lib timeout -k 10 300 python bench.py --full --cpu-sample -1 --steps ${STEPS:-60} --warmup 10 ${BENCH_ARGS:-} \
       --json-out "$OUT/bench_${n}_$rep.json" > "$OUT/bench_${n}_$rep.log" 2>&1
     rc=$?
     [ $rc -eq 0 ] || { echo "bench $n rc=$rc"; tail -5 "$OUT/bench_${n}_$rep.log"; exit $rc; }

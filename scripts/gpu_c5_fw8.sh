@@ -8,7 +8,7 @@ mkdir -p "$OUT"
 cd "$ROOT"
 run() {  # name env...
   local n=$1; shift
-  env "$@" timeout -k 10 300 python bench.py --dataset syn_web --steps 3 --warmup 1 --cpu-sample -1 \
+  env "$@" timeout -k 10 300 python bench.py --full --dataset syn_web --steps 3 --warmup 1 --cpu-sample -1 \
     --json-out "$OUT/$n.json" > "$OUT/$n.log" 2>&1
   local r=$?
   [ $r -eq 0 ] || { echo "$n rc=$r"; tail -5 "$OUT/$n.log"; exit $r; }

@@ -20,7 +20,7 @@ for rep in $(seq 1 ${REPS:-2}); do
   for v in "$@"; do
     n=${v%%=*}; e=${v#*=}
     envs=$(echo "$e" | tr ',' ' ')
-    env $envs timeout -k 10 300 python bench.py --dataset syn_web --steps 3 --warmup 1 --cpu-sample -1 \
+    env $envs timeout -k 10 300 python bench.py --full --dataset syn_web --steps 3 --warmup 1 --cpu-sample -1 \
       ${BENCH_ARGS:-} --json-out "$OUT/${n}_$rep.json" > "$OUT/${n}_$rep.log" 2>&1
     r=$?
     [ $r -eq 0 ] || { echo "$n rc=$r"; tail -5 "$OUT/${n}_$rep.log"; exit $r; }

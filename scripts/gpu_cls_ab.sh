@@ -15,7 +15,7 @@ rc=$?; echo "pytest rc=$rc"; tail -3 "$OUT/pytest.log"
 [ $rc -eq 0 ] || exit $rc
 run() {   # name env...
   local n=$1; shift
-  env "$@" timeout -k 10 300 python bench.py --gpus 1 --steps 20 --warmup 5 --cpu-sample -1 \
+  env "$@" timeout -k 10 300 python bench.py --full --gpus 1 --steps 20 --warmup 5 --cpu-sample -1 \
     --json-out "$OUT/bench_$n.json" > "$OUT/bench_$n.log" 2>&1
   local r=$?
   [ $r -eq 0 ] || { echo "bench $n rc=$r"; exit $r; }

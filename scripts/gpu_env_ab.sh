@@ -9,7 +9,7 @@ mkdir -p "$OUT"
 cd "$ROOT"
 run() {   # name, bench args, env settings...
   local name=$1 args=$2; shift 2
-  env "$@" timeout -k 10 300 python bench.py --cpu-sample -1 $args --json-out "$OUT/$name.json" \
+  env "$@" timeout -k 10 300 python bench.py --full --cpu-sample -1 $args --json-out "$OUT/$name.json" \
     > "$OUT/$name.log" 2>&1
   local rc=$?
   [ $rc -eq 0 ] || { echo "$name rc=$rc" | tee -a "$OUT/summary.txt"; exit $rc; }

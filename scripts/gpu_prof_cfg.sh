@@ -12,7 +12,7 @@ while [ $# -ge 2 ]; do
   OUT=$ROOT/gpurun_out/$TAG/$NAME
   mkdir -p "$OUT"
   timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$OUT/trace" -o run --output-format csv -- \
-    python3 "$ROOT/bench.py" $ARGS --cpu-sample -1 --json-out "$OUT/bench.json" > "$OUT/trace.log" 2>&1
+    python3 "$ROOT/bench.py" --full $ARGS --cpu-sample -1 --json-out "$OUT/bench.json" > "$OUT/trace.log" 2>&1
   rc=$?; echo "$NAME trace rc=$rc" | tee -a "$ROOT/gpurun_out/$TAG/summary.txt"
   [ $rc -eq 0 ] || exit $rc
   i=0
@@ -21,7 +21,7 @@ while [ $# -ge 2 ]; do
       "SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT GRBM_GUI_ACTIVE"; do
     i=$((i+1))
     timeout -s KILL 240 rocprofv3 --pmc $grp -d "$OUT/pass$i" -o run --output-format csv -- \
-      python3 "$ROOT/bench.py" $ARGS --steps 3 --warmup 1 --cpu-sample -1 > "$OUT/pass$i.log" 2>&1
+      python3 "$ROOT/bench.py" --full $ARGS --steps 3 --warmup 1 --cpu-sample -1 > "$OUT/pass$i.log" 2>&1
     rc=$?; echo "$NAME pmc$i rc=$rc" | tee -a "$ROOT/gpurun_out/$TAG/summary.txt"
     [ $rc -eq 0 ] || exit $rc
   done

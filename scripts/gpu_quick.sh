@@ -14,6 +14,6 @@ else
 fi
 rc=$?; echo "pytest_gpu rc=$rc"; tail -3 "$OUT/pytest_gpu.log"
 [ $rc -eq 0 ] || exit $rc
-timeout -k 10 300 python bench.py --cpu-sample -1 --json-out "$OUT/bench.json" > "$OUT/bench.log" 2>&1
+timeout -k 10 300 python bench.py --full --cpu-sample -1 --json-out "$OUT/bench.json" > "$OUT/bench.log" 2>&1
 rc=$?; echo "bench rc=$rc"; cat "$OUT/bench.json"
 exit $rc

@@ -15,7 +15,7 @@ rc=$?; echo "pytest rc=$rc"; tail -2 "$OUT/pytest.log"
 [ $rc -eq 0 ] || exit $rc
 c5() {  # name env...
   local n=$1; shift
-  env "$@" timeout -k 10 300 python bench.py --dataset syn_web --steps 3 --warmup 1 --cpu-sample -1 \
+  env "$@" timeout -k 10 300 python bench.py --full --dataset syn_web --steps 3 --warmup 1 --cpu-sample -1 \
     --json-out "$OUT/c5_$n.json" > "$OUT/c5_$n.log" 2>&1
   local r=$?
   [ $r -eq 0 ] || { echo "c5 $n rc=$r"; tail -5 "$OUT/c5_$n.log"; exit $r; }
@@ -34,7 +34,7 @@ if [ -f graphembedding_amd/lib/libsiamese_timing.so ] && [ -z "${SKIP_TIMING:-}"
 fi
 hb() {  # name env...
   local n=$1; shift
-  env "$@" timeout -k 10 300 python bench.py --gpus 1 --steps 20 --warmup 5 --cpu-sample -1 \
+  env "$@" timeout -k 10 300 python bench.py --full --gpus 1 --steps 20 --warmup 5 --cpu-sample -1 \
     --json-out "$OUT/c2_$n.json" > "$OUT/c2_$n.log" 2>&1
   local r=$?
   [ $r -eq 0 ] || { echo "c2 $n rc=$r"; tail -5 "$OUT/c2_$n.log"; exit $r; }

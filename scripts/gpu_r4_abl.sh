@@ -11,7 +11,7 @@ cd /tmp && export TMPDIR=/tmp
 for v in base FHASH FH1 FH2; do
   if [ $v = base ]; then LIBENV=""; else LIBENV="$ROOT/graphembedding_amd/lib/abl_$v.so"; fi
   SG_LIB=$LIBENV SG_WEB_PIPE=0 timeout -k 10 400 rocprofv3 --kernel-trace --stats -d "$OUT/$v" -o run \
-    --output-format csv -- python3 "$ROOT/bench.py" --dataset syn_web --steps 1 --warmup 1 \
+    --output-format csv -- python3 "$ROOT/bench.py" --full --dataset syn_web --steps 1 --warmup 1 \
     --cpu-sample -1 --json-out "$OUT/$v.json" > "$OUT/$v.log" 2>&1
   rc=$?; echo "$v rc=$rc"; [ $rc -eq 0 ] || exit $rc
   python3 - "$OUT/$v" <<'PY'

@@ -17,7 +17,7 @@ if [ "${SKIP_TESTS:-0}" != 1 ]; then
 fi
 run() {   # name env...
   local n=$1; shift
-  env "$@" timeout -k 10 400 python bench.py --dataset syn_web --steps 3 --warmup 1 --cpu-sample -1 \
+  env "$@" timeout -k 10 400 python bench.py --full --dataset syn_web --steps 3 --warmup 1 --cpu-sample -1 \
     --json-out "$OUT/bench_$n.json" > "$OUT/bench_$n.log" 2>&1
   local r=$?
   [ $r -eq 0 ] || { echo "bench $n rc=$r"; tail -5 "$OUT/bench_$n.log"; exit $r; }
@@ -31,14 +31,14 @@ done
 cd /tmp && export TMPDIR=/tmp
 export SG_WEB_PIPE=0
 timeout -k 10 400 rocprofv3 --kernel-trace --stats -d "$OUT/trace" -o run --output-format csv -- \
-  python3 "$ROOT/bench.py" --dataset syn_web --steps 1 --warmup 1 --cpu-sample -1 > "$OUT/trace.log" 2>&1
+  python3 "$ROOT/bench.py" --full --dataset syn_web --steps 1 --warmup 1 --cpu-sample -1 > "$OUT/trace.log" 2>&1
 rc=$?; echo "trace rc=$rc"; [ $rc -eq 0 ] || exit $rc
 i=0
 for grp in "SQ_WAVES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VALU_MFMA_BF16 SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE" \
            "FETCH_SIZE"; do
   i=$((i+1))
   timeout -s KILL 400 rocprofv3 --pmc $grp -d "$OUT/pmc$i" -o run --output-format csv -- \
-    python3 "$ROOT/bench.py" --dataset syn_web --steps 1 --warmup 1 --cpu-sample -1 > "$OUT/pmc$i.log" 2>&1
+    python3 "$ROOT/bench.py" --full --dataset syn_web --steps 1 --warmup 1 --cpu-sample -1 > "$OUT/pmc$i.log" 2>&1
   rc=$?; echo "pmc$i rc=$rc"; [ $rc -eq 0 ] || exit $rc
 done
 python3 "$ROOT/scripts/pmc_c5_summary.py" "$OUT" > "$OUT/pmc_summary.txt" 2>&1

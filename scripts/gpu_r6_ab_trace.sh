@@ -13,7 +13,7 @@ for v in prod ${VARIANTS:-}; do
   n=$(basename "$v" .so)
   if [ "$v" = prod ]; then L=""; else L="$ROOT/$v"; fi
   SG_LIB=$L timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$OUT/trace_$n" -o run --output-format csv -- \
-    python3 "$ROOT/bench.py" $TRACE_ARGS --cpu-sample -1 > "$OUT/trace_$n.log" 2>&1
+    python3 "$ROOT/bench.py" --full $TRACE_ARGS --cpu-sample -1 > "$OUT/trace_$n.log" 2>&1
   rc=$?; echo "trace $n rc=$rc" | tee -a "$OUT/summary.txt"
   [ $rc -eq 0 ] || exit $rc
 done

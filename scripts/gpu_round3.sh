@@ -10,7 +10,7 @@ ROOT=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$ROOT/gpurun_out/$TAG
 mkdir -p "$OUT"
 cd "$ROOT"
-BENCH="bench.py --gpus 1 --steps 20 --warmup 5"
+BENCH="bench.py --full --gpus 1 --steps 20 --warmup 5"
 if [ -z "$SKIP" ]; then
   timeout -k 10 900 python -u -m pytest tests -x -v -m gpu --timeout 300 --timeout-method thread \
     > "$OUT/pytest_gpu.log" 2>&1
@@ -26,7 +26,7 @@ rc=$?; echo "bench rc=$rc" | tee -a "$OUT/summary.txt"; cat "$OUT/bench.json"
 cd /tmp && export TMPDIR=/tmp
 # kernel trace only (no PMC, no other tracing domains), same command minus the CPU leg
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$OUT/trace" -o run --output-format csv -- \
-  python3 "$ROOT/bench.py" --gpus 1 --steps 20 --warmup 5 --cpu-sample -1 \
+  python3 "$ROOT/bench.py" --full --gpus 1 --steps 20 --warmup 5 --cpu-sample -1 \
   --json-out "$OUT/trace_bench.json" > "$OUT/trace.log" 2>&1
 rc=$?; echo "rocprof trace rc=$rc" | tee -a "$OUT/summary.txt"
 [ $rc -eq 0 ] || exit $rc
@@ -36,7 +36,7 @@ for grp in "FETCH_SIZE" "WRITE_SIZE" \
     "SQ_ACTIVE_INST_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_BRANCH GRBM_GUI_ACTIVE"; do
   i=$((i+1))
   timeout -s KILL 240 rocprofv3 --pmc $grp -d "$OUT/pmc$i" -o run --output-format csv -- \
-    python3 "$ROOT/bench.py" --gpus 1 --steps 3 --warmup 1 --cpu-sample -1 > "$OUT/pmc$i.log" 2>&1
+    python3 "$ROOT/bench.py" --full --gpus 1 --steps 3 --warmup 1 --cpu-sample -1 > "$OUT/pmc$i.log" 2>&1
   rc=$?; echo "pmc$i [$grp] rc=$rc" | tee -a "$OUT/summary.txt"
   [ $rc -eq 0 ] || exit $rc
 done

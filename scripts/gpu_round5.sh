@@ -25,7 +25,7 @@ if [ -z "$SKIP" ]; then
 fi
 ab() {   # name, env-prefix..., -- bench args
   local name=$1; shift
-  env "$@" timeout -k 10 300 python bench.py --cpu-sample -1 ${BENCH_ARGS_AB:-} \
+  env "$@" timeout -k 10 300 python bench.py --full --cpu-sample -1 ${BENCH_ARGS_AB:-} \
     --json-out "$OUT/ab_$name.json" > "$OUT/ab_$name.log" 2>&1
   local rc=$?
   [ $rc -eq 0 ] || { echo "ab $name rc=$rc" | tee -a "$OUT/summary.txt"; exit $rc; }

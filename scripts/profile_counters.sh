@@ -22,7 +22,7 @@ i=0
 for grp in "${GROUPS_LIST[@]}"; do
   i=$((i+1))
   timeout -k 10 300 rocprofv3 --pmc $grp -d "$ROOT/$OUT/pass$i" -o run --output-format csv -- \
-    python3 "$ROOT/bench.py" --steps 3 --warmup 1 --cpu-sample -1 ${BENCH_ARGS:-} > "$ROOT/$OUT/pass$i.log" 2>&1
+    python3 "$ROOT/bench.py" --full --steps 3 --warmup 1 --cpu-sample -1 ${BENCH_ARGS:-} > "$ROOT/$OUT/pass$i.log" 2>&1
   rc=$?
   echo "pass $i [$grp] rc=$rc" >> "$ROOT/$OUT/summary.txt"
   if [ $rc -ge 124 ]; then echo "stopping after rc=$rc"; exit $rc; fi

@@ -11,7 +11,7 @@ OUT=$ROOT/gpurun_out/$TAG
 mkdir -p "$OUT"
 cd "$ROOT"
 SG_LIB=graphembedding_amd/lib/libsiamese_timing.so timeout -k 10 120 python scripts/fast_timing.py 1 8 > "$OUT/timing.log" 2>&1
-timeout -k 10 120 python bench.py --emulate-world 8 --steps 200 --warmup 20 --cpu-sample -1 > "$OUT/emu8.log" 2>&1
+timeout -k 10 120 python bench.py --full --emulate-world 8 --steps 200 --warmup 20 --cpu-sample -1 > "$OUT/emu8.log" 2>&1
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 200 rocprofv3 --kernel-trace -d "$OUT/trace8" -o run --output-format csv -- \
-  python3 "$ROOT/bench.py" --emulate-world 8 --steps 50 --warmup 5 --cpu-sample -1 > "$OUT/trace8.log" 2>&1
+  python3 "$ROOT/bench.py" --full --emulate-world 8 --steps 50 --warmup 5 --cpu-sample -1 > "$OUT/trace8.log" 2>&1
