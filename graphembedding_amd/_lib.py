@@ -184,6 +184,17 @@ def lib():
     L.sg_fwd_bwd_src.argtypes = [pm, ps, vp, c_i64, c_i64, c_i64, vp, c_u64, vp, c_i32, vp, vp,
                                  vp, vp, vp]
     L.sg_fwd_bwd_src.restype = c_i32
+    # embed-once retrieval (include/siamese_embed.h, library 1.10)
+    L.sg_embed_dim.argtypes = [pm]
+    L.sg_embed_dim.restype = c_i32
+    L.sg_embed.argtypes = [pm, vp, vp, vp, c_i32, c_i32, vp, c_i64, vp, vp, vp, vp]
+    L.sg_embed.restype = c_i32
+    L.sg_score_grid_workspace_bytes.argtypes = [pm, c_i64]
+    L.sg_score_grid_workspace_bytes.restype = c_i64
+    L.sg_score_grid.argtypes = [pm, vp, vp, c_i64, c_i64, vp, c_i32, vp, c_i64, vp, vp]
+    L.sg_score_grid.restype = c_i32
+    L.sg_topk_rows.argtypes = [vp, c_i64, c_i64, c_i64, c_i32, c_i32, vp, vp, vp]
+    L.sg_topk_rows.restype = c_i32
     _lib = L
     return L
 
@@ -202,6 +213,11 @@ EXPORTED_SYMBOLS = ('sg_version', 'sg_record_bytes', 'sg_record_bytes_ex', 'sg_m
                     'sg_feed_step', 'sg_pair_order_src', 'sg_forward_src', 'sg_fwd_bwd_src',
                     'sg_pair_order_cls', 'sg_forward_cls', 'sg_fwd_bwd_cls', 'sg_train_step',
                     'sg_train_step_dseed')
+
+# the symbols of include/siamese_embed.h (a header of its own: EXPORTED_SYMBOLS stays the
+# symbol list of siamese_hip.h)
+EMBED_SYMBOLS = ('sg_embed_dim', 'sg_embed', 'sg_score_grid_workspace_bytes', 'sg_score_grid',
+                 'sg_topk_rows')
 
 # class_start entries of sg_pair_order_cls (include/siamese_hip.h SG_FAST_CLASSES_P1)
 FAST_CLASSES_P1 = 5
@@ -451,6 +467,46 @@ def fwd_bwd_src(m: SgModel, src: SgPairSource, n_pairs, pair_offset, batch_total
                                int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(y_stats), int(add_label_term),
                                _ptr(s_out), _ptr(grad_out), _ptr(loss_out), _ptr(workspace),
                                _stream(stream)), 'sg_fwd_bwd_src')
+
+
+def embed_dim(m: SgModel) -> int:
+    """Width E of one graph embedding (sg_embed_dim); raises for models it does not serve
+    (invalid, or the graph-store path)."""
+    e = int(lib().sg_embed_dim(ctypes.byref(m)))
+    if e < 0:
+        raise SiameseHipError('sg_embed_dim: model has no embedding kernel (invalid model or '
+                              'graph-store path)')
+    return e
+
+
+def embed(m: SgModel, store_dev, n_max, graph_idx, count, params, emb_out, status=None,
+          stream=None):
+    """sg_embed over a device dense store (adj, types, n) = GraphStore.to_device();
+    graph_idx int32 [count] device tensor or None (graphs 0 .. count-1)."""
+    adj, types, n = store_dev
+    check(lib().sg_embed(ctypes.byref(m), _ptr(adj), _ptr(types), _ptr(n), int(n.numel()),
+                         int(n_max), _ptr(graph_idx), int(count), _ptr(params), _ptr(emb_out),
+                         _ptr(status), _stream(stream)), 'sg_embed')
+
+
+def score_grid_workspace_bytes(m: SgModel, n_queries: int) -> int:
+    b = int(lib().sg_score_grid_workspace_bytes(ctypes.byref(m), int(n_queries)))
+    if b < 0:
+        raise SiameseHipError('sg_score_grid_workspace_bytes: the score grid serves the NTN '
+                              'head with input_dim <= 31 and feature_map_dim <= 16')
+    return b
+
+
+def score_grid(m: SgModel, emb_q, emb_db, n_q, n_db, params, apply_final, out, ld_out, workspace,
+               stream=None):
+    check(lib().sg_score_grid(ctypes.byref(m), _ptr(emb_q), _ptr(emb_db), int(n_q), int(n_db),
+                              _ptr(params), int(bool(apply_final)), _ptr(out), int(ld_out),
+                              _ptr(workspace), _stream(stream)), 'sg_score_grid')
+
+
+def topk_rows(vals, m, n, ld, k, largest, idx_out, val_out=None, stream=None):
+    check(lib().sg_topk_rows(_ptr(vals), int(m), int(n), int(ld), int(k), int(bool(largest)),
+                             _ptr(idx_out), _ptr(val_out), _stream(stream)), 'sg_topk_rows')
 
 
 def seed_advance(seed_dev, delta=1, stream=None):

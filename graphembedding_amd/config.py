@@ -63,6 +63,11 @@ DEFAULTS: Dict[str, Any] = dict(
     # / (m n) (a deviation from the reference, recorded on the result); 'per_pair' = one
     # timed single-pair launch per entry, as train.py:57-69 times each sess.run
     test_time='batched',
+    # how train.test scores the m x n test matrix: 'pairs' = every pair through the whole
+    # model (dropout on, as the reference's test runs, A4) | 'embed' = embed the m + n graphs
+    # once and fill the matrix with the NTN score grid (siamese_embed.h: inference mode,
+    # dropout off)
+    test_path='pairs',
     n_max=None,                # record node capacity (default: Padding max_in_dims or data max)
     record_dtype='f32',        # storage of Â in pair records: 'f32' | 'bf16' (config C3); fp32 math
     seed=123,                  # dropout RNG base seed (the reference's TF RNG was unseeded)

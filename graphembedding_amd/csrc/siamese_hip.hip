@@ -575,7 +575,7 @@ int64_t ntn_offset_floats(const PathChoice &c, int64_t n_pairs) {
 // ===========================================================================
 extern "C" {
 
-int32_t sg_version(void) { return 10900; }   /* 1.9.0: sg_train_step (gradient reduction + Adam in one launch) */
+int32_t sg_version(void) { return 11000; }   /* 1.10.0: embed-once retrieval (siamese_embed.h, sg_embed.hip) */
 
 int64_t sg_record_bytes(int32_t n_max) { return sg_record_bytes_ex(n_max, SG_DTYPE_F32); }
 

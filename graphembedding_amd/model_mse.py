@@ -490,6 +490,73 @@ class SiameseGCNTNMSE(object):
     def test_scores(self, batch: Batch, seed=None):
         return self.pred_sim_without_act(batch, seed).cpu().numpy().astype(np.float64)
 
+    # ---- embed-once retrieval (include/siamese_embed.h; inference mode: no dropout) ----
+    def _no_web(self, what):
+        if self.is_web:
+            raise _lib.SiameseHipError('{}: graph-store (Web) models have no embedding '
+                                       'kernels'.format(what))
+
+    @property
+    def embed_dim(self) -> int:
+        """Width of one graph embedding: the pair head's per-graph input."""
+        self._no_web('embed_dim')
+        return _lib.embed_dim(self.sg)
+
+    def embed(self, store: GraphStore, graph_idx=None):
+        """Graph-level embeddings [count][embed_dim] (torch, on the device) of the graphs
+        graph_idx (store ids, repeats allowed; None = every graph) of a GraphStore built at
+        this model's n_max.  Dropout is off whatever flags.dropout says."""
+        torch = self.torch
+        self._no_web('embed')
+        if store.n_max != self.n_max:
+            raise _lib.SiameseHipError('store n_max {} != model n_max {}'.format(store.n_max,
+                                                                                 self.n_max))
+        self.check_node_counts(store.n, 'embed')
+        idx = None
+        count = len(store)
+        if graph_idx is not None:
+            idx = torch.as_tensor(graph_idx, dtype=torch.int32, device=self.device).reshape(-1)
+            idx = idx.contiguous()
+            count = int(idx.numel())
+        out = torch.empty((count, self.embed_dim), dtype=torch.float32, device=self.device)
+        status = torch.zeros(1, dtype=torch.int32, device=self.device)
+        _lib.embed(self.sg, store.to_device(self.device), store.n_max, idx, count, self.params,
+                   out, status)
+        _lib.check(int(status.item()), 'sg_embed (device status)')
+        return out
+
+    def score_grid(self, emb_q, emb_db, final=True):
+        """Scores [m][n] of (query i as graph 1, database j as graph 2) from embeddings
+        (embed): the similarity (final activation applied) or, final=False, the
+        pre-activation score of pred_sim_without_act."""
+        torch = self.torch
+        self._no_web('score_grid')
+        d = self.embed_dim
+        q = torch.as_tensor(emb_q, dtype=torch.float32, device=self.device).contiguous()
+        db = torch.as_tensor(emb_db, dtype=torch.float32, device=self.device).contiguous()
+        if q.dim() != 2 or db.dim() != 2 or q.shape[1] != d or db.shape[1] != d:
+            raise _lib.SiameseHipError('score_grid: embeddings must be [*, {}]'.format(d))
+        m, n = int(q.shape[0]), int(db.shape[0])
+        ws = torch.empty(_lib.score_grid_workspace_bytes(self.sg, m) // 4 + 1,
+                         dtype=torch.float32, device=self.device)
+        out = torch.empty((m, n), dtype=torch.float32, device=self.device)
+        _lib.score_grid(self.sg, q, db, m, n, self.params, final, out, n, ws)
+        return out
+
+    def topk(self, scores, k, largest=True):
+        """(idx int32 [m][k], values [m][k]) of the k best entries of each row of scores:
+        by value, ties to the smaller column, NaN last."""
+        torch = self.torch
+        s = torch.as_tensor(scores, dtype=torch.float32, device=self.device)
+        if s.dim() != 2:
+            raise _lib.SiameseHipError('topk: scores must be [m][n]')
+        s = s.contiguous()
+        m, n = int(s.shape[0]), int(s.shape[1])
+        idx = torch.empty((m, max(int(k), 0)), dtype=torch.int32, device=self.device)
+        val = torch.empty((m, max(int(k), 0)), dtype=torch.float32, device=self.device)
+        _lib.topk_rows(s, m, n, n, k, largest, idx, val)
+        return idx, val
+
     def flat_params(self) -> np.ndarray:
         return self.params.detach().cpu().numpy()
 

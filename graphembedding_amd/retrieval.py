@@ -1,0 +1,36 @@
+"""Embed-once retrieval over a trained Siamese model (include/siamese_embed.h).
+
+The reference ranks a query against the database with one `sess.run` per (query,
+database) pair (model/Siamese/train.py:47-74).  An EmbeddingIndex runs the node stack of
+every database graph once, keeps the graph-level embeddings on the device, and scores
+queries against all of them with the NTN score-grid kernel; `topk` returns the most
+similar database graphs.  Inference mode: dropout is off (the reference leaves it on in
+its test runs, quirk A4), so an index is reproducible and independent of any seed.
+"""
+from __future__ import annotations
+
+from typing import Sequence
+
+from .packer import GraphStore
+
+
+class EmbeddingIndex(object):
+    def __init__(self, model, graphs: Sequence):
+        """model: SiameseGCNTNMSE (not a graph-store model); graphs: ModelGraphs."""
+        self.model = model
+        self.n = len(graphs)
+        self.embeddings = self._embed(graphs)       # torch float32 [n][embed_dim], device
+
+    def _embed(self, graphs: Sequence):
+        m = self.model
+        return m.embed(GraphStore(list(graphs), m.n_max, m.input_dim))
+
+    def scores(self, query_graphs: Sequence, final: bool = True):
+        """Similarity matrix [m][n] (torch, device): row i = query i as graph 1 against
+        every indexed graph as graph 2; final=False gives the pre-activation scores."""
+        return self.model.score_grid(self._embed(query_graphs), self.embeddings, final=final)
+
+    def topk(self, query_graphs: Sequence, k: int, largest: bool = True):
+        """(idx int32 [m][k], sims [m][k]): the k most similar indexed graphs per query,
+        best first, ties to the smaller index."""
+        return self.model.topk(self.scores(query_graphs), k, largest=largest)

@@ -71,6 +71,11 @@ def test(data, dist_calculator, model, flags=None, evaluator=None, verbose=True)
     """All m×n (test i, original train j) pairs in one launch (train.py:47-74)."""
     f = flags or FLAGS
     m, n = data.m_n()
+    test_path = getattr(f, 'test_path', 'pairs')
+    if test_path == 'embed':
+        return _test_embed(data, model, f, evaluator, verbose)
+    if test_path != 'pairs':
+        raise RuntimeError('Unknown test_path {}'.format(test_path))
     g1s, g2s = [], []
     for i in range(m):
         for j in range(n):
@@ -107,6 +112,38 @@ def test(data, dist_calculator, model, flags=None, evaluator=None, verbose=True)
         time_mat = np.full((m, n), elapsed * 1000.0 / max(1, m * n))   # msec per pair
     else:
         raise RuntimeError('Unknown test_time {}'.format(time_mode))
+    return _test_results(f, sims, time_mat, time_mode, elapsed, evaluator, verbose)
+
+
+def _test_embed(data, model, f, evaluator, verbose):
+    """test_path='embed': the m test and n original-train graphs go through the node stack
+    once each (model.embed) and the NTN score grid fills the matrix (model.score_grid),
+    instead of m·n runs of the whole model.  Inference mode: no dropout."""
+    from .packer import GraphStore
+    m, n = data.m_n()
+    time_mode = getattr(f, 'test_time', 'batched')
+    if time_mode == 'per_pair':
+        raise RuntimeError("test_time='per_pair' needs test_path='pairs': the embed path has "
+                           'no per-pair launch to time')
+    if time_mode != 'batched':
+        raise RuntimeError('Unknown test_time {}'.format(time_mode))
+    graphs = [data.test_data.get_graph(i) for i in range(m)] + \
+        [data.get_orig_train_graph(j) for j in range(n)]   # permuted after training (A6)
+    store = GraphStore(graphs, model.n_max, model.input_dim)
+    store.to_device(model.device)
+    _sync()
+    t0 = _time.time()
+    emb = model.embed(store)
+    s = model.score_grid(emb[:m], emb[m:], final=True)
+    _sync()
+    elapsed = _time.time() - t0
+    sims = s.cpu().numpy().astype(np.float64)
+    time_mat = np.full((m, n), elapsed * 1000.0 / max(1, m * n))   # msec per pair
+    return _test_results(f, sims, time_mat, time_mode, elapsed, evaluator, verbose)
+
+
+def _test_results(f, sims, time_mat, time_mode, elapsed, evaluator, verbose):
+    m, n = sims.shape
     if f.test_matrix == 'compat_diag':
         sim_mat = np.zeros((m, n))
         for i in range(m):

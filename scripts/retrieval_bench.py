@@ -1,0 +1,141 @@
+"""Embed-once retrieval against the pairwise path on the AIDS700nef-shaped set (GPU only).
+
+    python scripts/retrieval_bench.py [--repeats 3] [--iters 20] [--out FILE.json]
+
+Times, alternated `--repeats` times in one process (device events, warmed up):
+  (a) embed 700 graphs + sg_score_grid 700 x 700 with the final activation
+      (also its parts: sg_embed alone, sg_score_grid alone);
+  (b) the existing pairwise sg_forward_src over the same 490,000 pairs in class order
+      (the unchanged fused kernel: the yardstick), at the flags' dropout 0.1 (what
+      train.test runs today) and at dropout 0;
+  (c) sg_score_grid 4096 x 4096 from synthetic embeddings, with the write bandwidth of
+      its 4 B per pair of output.
+Prints one JSON line; (a) and (b) compute the same matrix up to dropout (checked at
+dropout 0 within 1e-4 before timing).
+"""
+import json
+import os
+import sys
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def _arg(name, default):
+    a = sys.argv[1:]
+    return type(default)(a[a.index(name) + 1]) if name in a else default
+
+
+def timed(fn, iters):
+    """msec per call of fn over `iters` back-to-back calls (device events)."""
+    import torch
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    a.record()
+    for _ in range(iters):
+        fn()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b) / iters
+
+
+def main():
+    import torch
+    from graphembedding_amd import _lib
+    from graphembedding_amd.allpairs import load_graph_set
+    from graphembedding_amd.config import Flags
+    from graphembedding_amd.model_mse import SiameseGCNTNMSE
+    if not torch.cuda.is_available():
+        raise SystemExit('retrieval_bench needs a GPU (there is no CPU fallback)')
+    dev = torch.device('cuda', 0)
+    repeats, iters = _arg('--repeats', 3), _arg('--iters', 20)
+    gs = load_graph_set('syn_aids700nef', n_max=10)
+    G = len(gs.mgs)
+    model = SiameseGCNTNMSE(gs.d_in, Flags(), device=dev, n_max=gs.n_max)            # dropout 0.1
+    model0 = SiameseGCNTNMSE(gs.d_in, Flags(dropout=0.0), device=dev, n_max=gs.n_max,
+                             params=model.flat_params())
+    store = gs.store
+    sdev = store.to_device(dev)
+    E = model.embed_dim
+
+    # (a) caller-owned buffers, as a serving loop would hold them
+    emb = torch.empty((G, E), dtype=torch.float32, device=dev)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    ws = torch.empty(_lib.score_grid_workspace_bytes(model.sg, G) // 4 + 1, dtype=torch.float32,
+                     device=dev)
+    sims = torch.empty((G, G), dtype=torch.float32, device=dev)
+
+    def embed():
+        _lib.embed(model.sg, sdev, store.n_max, None, G, model.params, emb, status)
+
+    def grid():
+        _lib.score_grid(model.sg, emb, emb, G, G, model.params, True, sims, G, ws)
+
+    def embed_grid():
+        embed()
+        grid()
+
+    # (b) the pairwise forward over the all-pairs grid of the store, class-ordered
+    def pairwise_of(mdl):
+        lab = torch.zeros(G * G, dtype=torch.float32, device=dev)
+        batch = mdl.balance(mdl.batch_from_store(store, G * G, lab))
+        s = torch.empty(G * G, dtype=torch.float32, device=dev)
+
+        def run():
+            _lib.forward_src(mdl.sg, batch.src, batch.n_pairs, 0, mdl.params, 1, s,
+                             order=batch.order)
+        return run, s, batch
+
+    pair01, s01, keep01 = pairwise_of(model)
+    pair00, s00, keep00 = pairwise_of(model0)
+
+    # (c) a 4096 x 4096 grid from synthetic embeddings
+    N = 4096
+    rng = np.random.default_rng(0)
+    syn = torch.from_numpy(rng.uniform(0, 1, size=(N, E)).astype(np.float32)).to(dev)
+    ws_c = torch.empty(_lib.score_grid_workspace_bytes(model.sg, N) // 4 + 1,
+                       dtype=torch.float32, device=dev)
+    out_c = torch.empty((N, N), dtype=torch.float32, device=dev)
+
+    def grid_c():
+        _lib.score_grid(model.sg, syn, syn, N, N, model.params, True, out_c, N, ws_c)
+
+    # same matrix at dropout 0 (the pairwise scores are pre-activation)
+    embed_grid()
+    pair00()
+    torch.cuda.synchronize()
+    assert int(status.item()) == 0
+    want = np.exp(-model.flags.yeta * s00.cpu().numpy().astype(np.float64) ** 2).reshape(G, G)
+    err = float(np.abs(sims.cpu().numpy() - want).max())
+    assert err <= 1e-4, err
+
+    cases = [('embed_grid_700', embed_grid), ('embed_700', embed), ('grid_700', grid),
+             ('pairwise_700_dropout0.1', pair01), ('pairwise_700_dropout0', pair00),
+             ('grid_4096', grid_c)]
+    for _, fn in cases:          # warm-up of every shape
+        timed(fn, 3)
+    ms = {k: [] for k, _ in cases}
+    for _ in range(repeats):     # alternated
+        for k, fn in cases:
+            ms[k].append(timed(fn, iters))
+    med = {k: float(np.median(v)) for k, v in ms.items()}
+    res = dict(graphs=G, pairs=G * G, embed_dim=E, repeats=repeats, iters=iters,
+               max_abs_sim_diff_dropout0=err, msec=ms, msec_median=med,
+               pairwise_over_embed_grid=dict(
+                   dropout01=med['pairwise_700_dropout0.1'] / med['embed_grid_700'],
+                   dropout0=med['pairwise_700_dropout0'] / med['embed_grid_700']),
+               grid_4096_write_GBps=N * N * 4 / (med['grid_4096'] * 1e-3) / 1e9,
+               grid_4096_Gpairs_per_s=N * N / (med['grid_4096'] * 1e-3) / 1e9,
+               device=torch.cuda.get_device_name(0))
+    line = json.dumps(res)
+    print(line)
+    out = _arg('--out', '')
+    if out:
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+        with open(out, 'w') as f:
+            f.write(line + '\n')
+
+
+if __name__ == '__main__':
+    main()
