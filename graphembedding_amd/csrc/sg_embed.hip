@@ -10,11 +10,7 @@
 #include "../../include/siamese_embed.h"
 #include "sg_gen_nodes.h"
 #include "sg_mfma.h"
-
-int sg_num_cus();
-// graph-store path (sg_web.hip): its models are not served here
-int sg_web_plan_params(const sg_model_t *m, int64_t *n_params);
-int sg_web_lds_ok(const sg_model_t *m);
+#include "sg_paths.h"
 
 namespace {
 

@@ -27,16 +27,14 @@
 // one slab row per workgroup (deterministic).
 #include <type_traits>
 
-#include "sg_plan.h"
 #include "sg_mfma.h"
-
-int sg_num_cus();
+#include "sg_paths.h"
 
 namespace {
 
 using namespace sgk;
 
-constexpr int FH1 = 32, FH2 = 16, FK = 10;
+constexpr int FH1 = kSgH1, FH2 = kSgH2, FK = kSgK;
 constexpr int TS1 = 36;  // D1 tile row stride (floats)
 constexpr int TS2 = 20;  // gZ1 tile row stride
 constexpr int W1S = 20;  // W1 table row stride (16 + pad)
@@ -1105,6 +1103,7 @@ __global__ void __launch_bounds__(64 * MAXW) sg_fast_kernel(FastArgs A) {
         // prefetch a vmcnt(0), which also waited for this pair's stores (their HBM latency,
         // every pair).
         static_assert(DN == 16 && XO2 == 16, "the compact row holds 16-element x1 and x2");
+        static_assert(FK <= 14, "gm fills slots 32.., slot 46 stays 0 and slot 47 the 1");
         float *nb_ = A.ntn + (size_t)(uint32_t)pcur * 48u;
         {
           const float xv = sX[l & 31];
@@ -1551,19 +1550,11 @@ void launch_fast(const FastCfg &c, bool bwd, bool aligned, bool intended,
 // Pooled-head stacks (tuning.py:66-93): GCN(d_in→32, relu) → GCN(32→16) → Average or
 // Attention(16) (layers.py:121-160) → NTN(16, K=10)
 static bool fast_pool_shape(const sg_model_t *m, const SgGenPlan &P) {
-  if (m->num_layers != 4) return false;
+  if (m->num_layers != 4 || !sg_gcn_prefix_shape(m)) return false;
   const sg_layer_t *Ly = m->layers;
-  if (Ly[0].kind != SG_GCN || !Ly[0].sparse_inputs || Ly[0].output_dim != FH1 ||
-      Ly[0].act != SG_ACT_RELU || !Ly[0].bias)
-    return false;
-  if (Ly[1].kind != SG_GCN || Ly[1].input_dim != FH1 || Ly[1].output_dim != FH2 ||
-      Ly[1].act != SG_ACT_IDENTITY || !Ly[1].bias)
-    return false;
   if (Ly[2].kind != SG_AVERAGE && !(Ly[2].kind == SG_ATTENTION && Ly[2].input_dim == FH2))
     return false;
-  if (Ly[3].kind != SG_NTN || Ly[3].input_dim != FH2 || Ly[3].output_dim != FK ||
-      Ly[3].act != SG_ACT_RELU || !Ly[3].bias)
-    return false;
+  if (!sg_ntn_head_shape(Ly[3], FH2)) return false;
   if (m->n_max != 10 && m->n_max != 12) return false;
   if (m->final_act != SG_FINAL_GAUSSIAN) return false;
   if (m->d_in > 32) return false;
@@ -1572,25 +1563,8 @@ static bool fast_pool_shape(const sg_model_t *m, const SgGenPlan &P) {
 
 static bool fast_shape(const sg_model_t *m, const SgGenPlan &P) {
   if (fast_pool_shape(m, P)) return true;
-  if (m->num_layers != 5) return false;
-  const sg_layer_t *Ly = m->layers;
-  if (Ly[0].kind != SG_GCN || !Ly[0].sparse_inputs || Ly[0].output_dim != FH1 ||
-      Ly[0].act != SG_ACT_RELU || !Ly[0].bias)
-    return false;
-  if (Ly[1].kind != SG_GCN || Ly[1].input_dim != FH1 || Ly[1].output_dim != FH2 ||
-      Ly[1].act != SG_ACT_IDENTITY || !Ly[1].bias)
-    return false;
-  if (Ly[2].kind != SG_DENSE || Ly[2].input_dim != FH2 || Ly[2].output_dim != 1 ||
-      Ly[2].act != SG_ACT_RELU || !Ly[2].bias)
-    return false;
-  if (Ly[3].kind != SG_PADDING || Ly[3].padding_value != 0.f) return false;
-  const int D = Ly[3].output_dim;
-  if (Ly[4].kind != SG_NTN || Ly[4].input_dim != D || Ly[4].output_dim != FK ||
-      Ly[4].act != SG_ACT_RELU || !Ly[4].bias)
-    return false;
+  const int D = sg_default_stack_dim(m);
   if (m->n_max != D || (D != 10 && D != 12)) return false;
-  if (m->final_act != SG_FINAL_GAUSSIAN) return false;
-  if (m->d_in > 32) return false;   // two 16-row type tiles for the one-hot gW0 MFMA
   return P.n_params > 0;
 }
 
@@ -1673,43 +1647,31 @@ static XcdWeights xcd_weights_from_env() {
   return x;
 }
 
-int sg_ntn_wgrad_run(const float *ntn, int64_t n_pairs, int D, int oW, int oV, int obn, int C,
-                     float *slab, int blocks, hipStream_t st, bool compact);
-
 // The host side of sg_fast_run.  The translation unit sg_fast_att.hip compiles this file
 // again with SG_FAST_ATT_TU defined and instantiates only the Attention kernels (the
 // default TU instantiates the rest): the two compile in parallel.
-static int fast_run_impl(const sg_model_t *m, const SgGenPlan &P, bool bwd, const void *recs,
-                         const int32_t *order, int64_t n_pairs, int64_t pair_offset,
-                         int64_t batch_total, const float *params, uint64_t seed,
-                         const float *y_stats, float *s_out, float *slab, float *ntn,
-                         int *blocks_out, hipStream_t stream, const uint64_t *seed_dev,
-                         const sg_pair_source_t *src, const int32_t *class_start,
-                         const SgAdamPre *adam_pre) {
+static int fast_run_impl(const sg_model_t *m, const SgGenPlan &P, const SgPairRun &r,
+                         int *blocks_out) {
   const int D = P.n_max;
+  const bool bwd = r.bwd;
+  const int64_t n_pairs = r.n_pairs;
+  float *const slab = r.slab, *const ntn = r.ntn;
+  const hipStream_t stream = r.stream;
   FastCfg c = fast_cfg(P, n_pairs, bwd);
   // the kernel indexes pairs in 32 bits (2^31 records would be ≥ 1 TB)
   if (n_pairs > 0x7FFFFFFF - (int64_t)c.blocks * c.waves * 2) return SG_ERR_ARG;
-  FastArgs A;
-  A.recs = (const uint8_t *)recs;
-  A.src_store = src ? 1 : 0;
-  A.G = src ? src->n_graphs : 0;
-  A.sadj = src ? src->adj : nullptr;
-  A.stypes = src ? src->types : nullptr;
-  A.sn = src ? src->n : nullptr;
-  A.spairs = src ? src->pair_idx : nullptr;
-  A.grid_base = src ? src->grid_base : 0;
-  A.slabels = src ? src->labels : nullptr;
-  A.status = src ? src->status : nullptr;
-  if (src && (P.adj_dtype != SG_DTYPE_F32 || src->n_max != D || src->n_graphs <= 0))
+  if (r.src && (P.adj_dtype != SG_DTYPE_F32 || r.src->n_max != D || r.src->n_graphs <= 0))
     return SG_ERR_ARG;
-  A.order = order;
-  A.cls = order ? class_start : nullptr;
+  const bool avg = plan_avg(P);   // NTN is layer 3 after Average / Attention
+  const bool att = plan_att(P);
+  FastArgs A;
+  sg_fill_pair_args(A, m, P, r, avg ? 3 : 4, !avg, c.shared_floats, c.wave_floats);
+  A.cls = r.order ? r.class_start : nullptr;
   // the class-exclusive schedule gives each class waves in proportion to count x cost
   // (class_weights_for; SG_CLS_W="w0,w1,w2,w3" to tune); the environment is parsed once
   // per process, and only for class-scheduled launches
   if (A.cls) {
-    class_weights_for(plan_avg(P), plan_att(P), P.adj_dtype == SG_DTYPE_BF16, bwd, A.cw);
+    class_weights_for(avg, att, P.adj_dtype == SG_DTYPE_BF16, bwd, A.cw);
     static const XcdWeights xwt = xcd_weights_from_env();
     for (int k = 0; k < 8; ++k) A.xw[k] = xwt.w[k];
   } else {
@@ -1718,59 +1680,19 @@ static int fast_run_impl(const sg_model_t *m, const SgGenPlan &P, bool bwd, cons
   }
   A.xw_even = 1;
   for (int k = 1; k < 8; ++k) A.xw_even &= A.xw[k] == A.xw[0] ? 1 : 0;
-  A.n_pairs = n_pairs;
-  A.rw4h = P.hbm_words / 4;
-  A.rec_bf16 = P.adj_dtype == SG_DTYPE_BF16 ? 1 : 0;
-  A.pair_offset = pair_offset;
-  A.params = params;
-  A.y_stats = y_stats;
-  A.s_out = s_out;
-  A.slab = slab;
-  A.ntn = ntn;
-  A.key = sg_seed_key(seed);
-  A.seed_dev = seed_dev;
+  A.seed_dev = r.seed_dev;
   A.ad_bp = nullptr;
   A.ad_out = nullptr;
   A.ad_lr = A.ad_b1 = A.ad_b2 = A.ad_wd = 0.f;
-  if (bwd && adam_pre != nullptr) {
-    A.ad_bp = adam_pre->bp;
-    A.ad_out = adam_pre->out;
-    A.ad_lr = adam_pre->lr;
-    A.ad_b1 = adam_pre->b1;
-    A.ad_b2 = adam_pre->b2;
-    A.ad_wd = adam_pre->wd;
+  if (bwd && r.adam_pre != nullptr) {
+    A.ad_bp = r.adam_pre->bp;
+    A.ad_out = r.adam_pre->out;
+    A.ad_lr = r.adam_pre->lr;
+    A.ad_b1 = r.adam_pre->b1;
+    A.ad_b2 = r.adam_pre->b2;
+    A.ad_wd = r.adam_pre->wd;
   }
-  const float keep = m->keep_prob;
-  const bool avg = plan_avg(P);   // NTN is layer 3 after Average / Attention
-  const bool att = plan_att(P);
-  const float k0 = m->layers[0].dropout ? keep : 1.f, k1 = m->layers[1].dropout ? keep : 1.f;
-  const float k2 = (!avg && m->layers[2].dropout) ? keep : 1.f;
-  const float k4 = m->layers[avg ? 3 : 4].dropout ? keep : 1.f;
-  A.thr0 = sg_keep_threshold(k0);
-  A.thr1 = sg_keep_threshold(k1);
-  A.thr2 = sg_keep_threshold(k2);
-  A.thr4 = sg_keep_threshold(k4);
-  A.ik0 = 1.f / k0;
-  A.ik1 = 1.f / k1;
-  A.ik2 = 1.f / k2;
-  A.ik4 = 1.f / k4;
-  A.yeta = m->yeta;
-  A.inv_batch = batch_total > 0 ? 1.f / (float)batch_total : 0.f;
-  A.d_in = P.d_in;
-  A.n_params = P.n_params;
-  A.shared_floats = c.shared_floats;
-  A.wave_floats = c.wave_floats;
-  A.oW0 = P.L[0].offW;
-  A.ob0 = P.L[0].offB;
-  A.oW1 = P.L[1].offW;
-  A.ob1 = P.L[1].offB;
-  A.oWd = avg ? -1 : P.L[2].offW;
-  A.obd = avg ? -1 : P.L[2].offB;
   A.oWa = att ? P.L[2].offW : -1;
-  A.oW = P.offW;
-  A.oV = P.offV;
-  A.oU = P.offU;
-  A.obn = P.offB;
   const bool aligned = m->loss_mode == SG_LOSS_ALIGNED;
   const bool intended = m->ntn_mode == SG_NTN_INTENDED;
   if (avg && bwd && !ntn) return SG_ERR_ARG;
@@ -1798,24 +1720,11 @@ static int fast_run_impl(const sg_model_t *m, const SgGenPlan &P, bool bwd, cons
 }
 
 #ifdef SG_FAST_ATT_TU
-int sg_fast_att_run(const sg_model_t *m, const SgGenPlan &P, bool bwd, const void *recs,
-                    const int32_t *order, int64_t n_pairs, int64_t pair_offset,
-                    int64_t batch_total, const float *params, uint64_t seed,
-                    const float *y_stats, float *s_out, float *slab, float *ntn, int *blocks_out,
-                    hipStream_t stream, const uint64_t *seed_dev, const sg_pair_source_t *src,
-                    const int32_t *class_start, const SgAdamPre *adam_pre) {
-  return fast_run_impl(m, P, bwd, recs, order, n_pairs, pair_offset, batch_total, params, seed,
-                       y_stats, s_out, slab, ntn, blocks_out, stream, seed_dev, src, class_start,
-                       adam_pre);
+int sg_fast_att_run(const sg_model_t *m, const SgGenPlan &P, const SgPairRun &r,
+                    int *blocks_out) {
+  return fast_run_impl(m, P, r, blocks_out);
 }
 #else
-int sg_fast_att_run(const sg_model_t *m, const SgGenPlan &P, bool bwd, const void *recs,
-                    const int32_t *order, int64_t n_pairs, int64_t pair_offset,
-                    int64_t batch_total, const float *params, uint64_t seed,
-                    const float *y_stats, float *s_out, float *slab, float *ntn, int *blocks_out,
-                    hipStream_t stream, const uint64_t *seed_dev, const sg_pair_source_t *src,
-                    const int32_t *class_start, const SgAdamPre *adam_pre);
-
 int sg_fast_supported(const sg_model_t *m, const SgGenPlan &P) {
   if (getenv("SG_DISABLE_FAST")) return 0;
   return fast_shape(m, P) ? 1 : 0;
@@ -1828,19 +1737,8 @@ int64_t sg_fast_slab_floats(const SgGenPlan &P, int64_t n_pairs) {
 
 int sg_fast_needs_ntn(const SgGenPlan &P) { return plan_avg(P) ? 1 : 0; }
 
-int sg_fast_run(const sg_model_t *m, const SgGenPlan &P, bool bwd, const void *recs,
-                const int32_t *order, int64_t n_pairs, int64_t pair_offset, int64_t batch_total,
-                const float *params, uint64_t seed, const float *y_stats, float *s_out,
-                float *slab, float *ntn, int *blocks_out, hipStream_t stream,
-                const uint64_t *seed_dev, const sg_pair_source_t *src,
-                const int32_t *class_start, const SgAdamPre *adam_pre) {
-  if (plan_att(P))
-    return sg_fast_att_run(m, P, bwd, recs, order, n_pairs, pair_offset, batch_total, params,
-                           seed, y_stats, s_out, slab, ntn, blocks_out, stream, seed_dev, src,
-                           class_start, adam_pre);
-  return fast_run_impl(m, P, bwd, recs, order, n_pairs, pair_offset, batch_total, params, seed,
-                       y_stats, s_out, slab, ntn, blocks_out, stream, seed_dev, src, class_start,
-                       adam_pre);
+int sg_fast_run(const sg_model_t *m, const SgGenPlan &P, const SgPairRun &r, int *blocks_out) {
+  return plan_att(P) ? sg_fast_att_run(m, P, r, blocks_out) : fast_run_impl(m, P, r, blocks_out);
 }
 #endif
 

@@ -23,14 +23,12 @@
 #include <type_traits>
 
 #include "sg_mfma.h"
-#include "sg_plan.h"
-
-int sg_num_cus();
+#include "sg_paths.h"
 
 namespace {
 using namespace sgk;
 
-constexpr int FH1 = 32, FH2 = 16, FK = 10;
+constexpr int FH1 = kSgH1, FH2 = kSgH2, FK = kSgK;
 constexpr int NC = 32;     // record node capacity
 constexpr int TS1 = 36;    // D1 transpose tile row stride
 constexpr int W1S = 20;    // W1·ik1 [32][16] row stride
@@ -1041,25 +1039,9 @@ F32Cfg f32_cfg(const SgGenPlan &P, int64_t n_pairs, bool bwd) {
 // --------------------------------------------------------------------------
 int sg_fast32_supported(const sg_model_t *m, const SgGenPlan &P) {
   if (getenv("SG_DISABLE_FAST")) return 0;
-  if (m->num_layers != 5) return 0;
-  const sg_layer_t *Ly = m->layers;
-  if (Ly[0].kind != SG_GCN || !Ly[0].sparse_inputs || Ly[0].output_dim != FH1 ||
-      Ly[0].act != SG_ACT_RELU || !Ly[0].bias)
-    return 0;
-  if (Ly[1].kind != SG_GCN || Ly[1].input_dim != FH1 || Ly[1].output_dim != FH2 ||
-      Ly[1].act != SG_ACT_IDENTITY || !Ly[1].bias)
-    return 0;
-  if (Ly[2].kind != SG_DENSE || Ly[2].input_dim != FH2 || Ly[2].output_dim != 1 ||
-      Ly[2].act != SG_ACT_RELU || !Ly[2].bias)
-    return 0;
-  if (Ly[3].kind != SG_PADDING || Ly[3].padding_value != 0.f) return 0;
-  const int D = Ly[3].output_dim;
-  if (Ly[4].kind != SG_NTN || Ly[4].input_dim != D || Ly[4].output_dim != FK ||
-      Ly[4].act != SG_ACT_RELU || !Ly[4].bias)
-    return 0;
+  const int D = sg_default_stack_dim(m);
   if (m->n_max != NC || D <= 12 || D >= NC) return 0;   // slot D of x holds the 1
-  if (m->final_act != SG_FINAL_GAUSSIAN) return 0;
-  if (m->d_in > 32 || m->d_in < 1) return 0;
+  if (m->d_in < 1) return 0;
   // LDS: the shared tables, 8 wave regions and the flush must fit one CU
   const size_t lds = (size_t)(Lds32::shared_floats(m->d_in, D) + MAXW * Lds32::WAVE) * 4u;
   if (lds > 163840u) return 0;
@@ -1083,6 +1065,7 @@ int sg_ntn_wgrad_run(const float *ntn, int64_t n_pairs, int D, int oW, int oV, i
   if (D < 1 || D > 31 || obn < 0 || (compact && D != 16)) return SG_ERR_ARG;
   // column tiles: ceil((D + 1) K / 16)
   const int nct = ((D + 1) * FK + 15) / 16;
+  if (compact && nct > 16) return SG_ERR_ARG;   // 8 waves of 2 column tiles
   // D <= 15: rows a <= D fit the first tile; D = 16: row a = 16 on VALU
   if (compact)   // 8 waves of 2 tiles, compact rows
     hipLaunchKernelGGL((sg_ntn_wgrad_kernel<2, false, 8, NBUF16>), dim3(blocks), dim3(512), 0,
@@ -1096,72 +1079,25 @@ int sg_ntn_wgrad_run(const float *ntn, int64_t n_pairs, int D, int oW, int oV, i
   return hipGetLastError() == hipSuccess ? SG_OK : SG_ERR_HIP;
 }
 
-int sg_fast32_run(const sg_model_t *m, const SgGenPlan &P, bool bwd, const void *recs,
-                  const int32_t *order, int64_t n_pairs, int64_t pair_offset,
-                  int64_t batch_total, const float *params, uint64_t seed, const float *y_stats,
-                  float *s_out, float *slab, float *ntn, int *blocks_out, hipStream_t stream,
-                  const sg_pair_source_t *src) {
+int sg_fast32_run(const sg_model_t *m, const SgGenPlan &P, const SgPairRun &r, int *blocks_out) {
+  const bool bwd = r.bwd;
+  const int64_t n_pairs = r.n_pairs;
+  const sg_pair_source_t *src = r.src;
+  const hipStream_t stream = r.stream;
   const F32Cfg c = f32_cfg(P, n_pairs, bwd);
   if (n_pairs > 0x7FFFFFFF - (int64_t)c.blocks * c.waves * 2) return SG_ERR_ARG;
+  if (src && (P.adj_dtype != SG_DTYPE_F32 || src->n_max != NC || src->n_graphs <= 0 ||
+              !src->adj || !src->types || !src->n))
+    return SG_ERR_ARG;
   F32Args A;
-  A.recs = (const uint8_t *)recs;
-  A.src_store = src ? 1 : 0;
-  A.G = src ? src->n_graphs : 0;
-  A.sadj = src ? (const uint4 *)src->adj : nullptr;
-  A.stypes = src ? (const uint4 *)src->types : nullptr;
-  A.sn = src ? src->n : nullptr;
-  A.spairs = src ? src->pair_idx : nullptr;
-  A.grid_base = src ? src->grid_base : 0;
+  sg_fill_pair_args(A, m, P, r, 4, true, c.shared_floats, c.wave_floats);
+  A.D = P.D;
   {
     const uint64_t G = src ? (uint64_t)(src->n_graphs > 0 ? src->n_graphs : 1) : 1u;
     A.g32 = (src && src->pair_idx == nullptr && G * G <= 0xFFFFFFFFull &&
              src->grid_base >= 0 && (uint64_t)src->grid_base + (uint64_t)n_pairs <= G * G) ? 1 : 0;
     A.gm = (uint32_t)(((1ull << 32) + G - 1) / G);   // ceil(2^32 / G) (G >= 2: fits 32 bits)
   }
-  A.slabels = src ? src->labels : nullptr;
-  A.status = src ? src->status : nullptr;
-  if (src && (P.adj_dtype != SG_DTYPE_F32 || src->n_max != NC || src->n_graphs <= 0 ||
-              !src->adj || !src->types || !src->n))
-    return SG_ERR_ARG;
-  A.order = order;
-  A.n_pairs = n_pairs;
-  A.pair_offset = pair_offset;
-  A.rw4h = P.hbm_words / 4;
-  A.rec_bf16 = P.adj_dtype == SG_DTYPE_BF16 ? 1 : 0;
-  A.params = params;
-  A.y_stats = y_stats;
-  A.s_out = s_out;
-  A.slab = slab;
-  A.ntn = ntn;
-  A.key = sg_seed_key(seed);
-  const float keep = m->keep_prob;
-  const float k0 = m->layers[0].dropout ? keep : 1.f, k1 = m->layers[1].dropout ? keep : 1.f;
-  const float k2 = m->layers[2].dropout ? keep : 1.f, k4 = m->layers[4].dropout ? keep : 1.f;
-  A.thr0 = sg_keep_threshold(k0);
-  A.thr1 = sg_keep_threshold(k1);
-  A.thr2 = sg_keep_threshold(k2);
-  A.thr4 = sg_keep_threshold(k4);
-  A.ik0 = 1.f / k0;
-  A.ik1 = 1.f / k1;
-  A.ik2 = 1.f / k2;
-  A.ik4 = 1.f / k4;
-  A.yeta = m->yeta;
-  A.inv_batch = batch_total > 0 ? 1.f / (float)batch_total : 0.f;
-  A.d_in = P.d_in;
-  A.n_params = P.n_params;
-  A.D = P.D;
-  A.shared_floats = c.shared_floats;
-  A.wave_floats = c.wave_floats;
-  A.oW0 = P.L[0].offW;
-  A.ob0 = P.L[0].offB;
-  A.oW1 = P.L[1].offW;
-  A.ob1 = P.L[1].offB;
-  A.oWd = P.L[2].offW;
-  A.obd = P.L[2].offB;
-  A.oW = P.offW;
-  A.oV = P.offV;
-  A.oU = P.offU;
-  A.obn = P.offB;
   const bool aligned = m->loss_mode == SG_LOSS_ALIGNED;
   const bool intended = m->ntn_mode == SG_NTN_INTENDED;
   auto launch = [&](const void *fn, auto kern) {
@@ -1183,8 +1119,8 @@ int sg_fast32_run(const sg_model_t *m, const SgGenPlan &P, bool bwd, const void 
   }
 #undef SG32_LAUNCH
   if (bwd) {
-    const int rc = sg_ntn_wgrad_run((const float *)ntn, n_pairs, P.D, P.offW, P.offV, P.offB,
-                                    P.n_params + 1, slab, c.blocks, stream, false);
+    const int rc = sg_ntn_wgrad_run(r.ntn, n_pairs, P.D, P.offW, P.offV, P.offB, P.n_params + 1,
+                                    r.slab, c.blocks, stream, false);
     if (rc != SG_OK) return rc;
   }
   if (blocks_out) *blocks_out = c.blocks;

@@ -10,6 +10,7 @@
 // (Attention), 192-205 (Dense), 223-227 (Padding), 249-252 (Dot), 282-310
 // (NTN), 332-338 (sparse dropout); models.py:39-88; model_mse.py:117-151.
 #include "sg_gen_nodes.h"   // gen_forward_nodes, rows_of (shared with sg_embed.hip)
+#include "sg_paths.h"
 
 namespace {
 
@@ -345,8 +346,6 @@ struct SgGenLaunch {
   size_t lds_bytes;
 };
 
-int sg_num_cus();
-
 static SgGenLaunch sg_generic_launch(const SgGenPlan &P, int64_t n_pairs, bool bwd) {
   SgGenLaunch L;
   const size_t gbytes = bwd ? (size_t)((P.n_params + 1 + 3) & ~3) * 4u : 0u;
@@ -374,23 +373,22 @@ int64_t sg_generic_slab_floats(const SgGenPlan &P, int64_t n_pairs) {
   return (int64_t)L.blocks * (P.n_params + 1);
 }
 
-int sg_generic_run(const SgGenPlan &P, bool bwd, const void *recs, const int32_t *order,
-                   int64_t n_pairs, int64_t pair_offset, int64_t batch_total, const float *params, uint64_t seed,
-                   const float *y_stats, float *s_out, float *slab, int *blocks_out,
-                   hipStream_t stream) {
-  SgGenLaunch L = sg_generic_launch(P, n_pairs, bwd);
+int sg_generic_run(const SgGenPlan &P, const SgPairRun &r, int *blocks_out) {
+  const bool bwd = r.bwd;
+  const hipStream_t stream = r.stream;
+  SgGenLaunch L = sg_generic_launch(P, r.n_pairs, bwd);
   if (L.lds_bytes > 163840u) return SG_ERR_UNSUPPORTED;
   GenArgs A;
-  A.recs = (const uint8_t *)recs;
-  A.order = order;
-  A.n_pairs = n_pairs;
-  A.pair_offset = pair_offset;
-  A.inv_batch = batch_total > 0 ? 1.f / (float)batch_total : 0.f;
-  A.params = params;
-  A.key = sg_seed_key(seed);
-  A.y_stats = y_stats;
-  A.s_out = s_out;
-  A.slab = slab;
+  A.recs = (const uint8_t *)r.recs;
+  A.order = r.order;
+  A.n_pairs = r.n_pairs;
+  A.pair_offset = r.pair_offset;
+  A.inv_batch = r.batch_total > 0 ? 1.f / (float)r.batch_total : 0.f;
+  A.params = r.params;
+  A.key = sg_seed_key(r.seed);
+  A.y_stats = r.y_stats;
+  A.s_out = r.s_out;
+  A.slab = r.slab;
   if (L.lds_bytes > 65536u) {
     (void)hipFuncSetAttribute(bwd ? (const void *)sg_generic_kernel<true>
                             : (const void *)sg_generic_kernel<false>,

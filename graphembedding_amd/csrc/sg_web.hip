@@ -35,10 +35,8 @@
 #include <type_traits>
 #include <vector>
 
-#include "sg_common.h"
 #include "sg_mfma.h"
-
-int sg_num_cus();
+#include "sg_paths.h"
 
 namespace {
 using sgk::f4;

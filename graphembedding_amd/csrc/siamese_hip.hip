@@ -3,7 +3,7 @@
 // statistics, the deterministic gradient-slab reduction and TF-form Adam.
 #include <mutex>
 
-#include "sg_plan.h"
+#include "sg_paths.h"
 
 // ---------------------------------------------------------------------------
 // Device properties
@@ -21,43 +21,6 @@ int sg_num_cus() {
   }
   return cache[dev];
 }
-
-// generic path (sg_generic.hip)
-int sg_generic_lds_ok(const SgGenPlan &P, bool bwd);
-int64_t sg_generic_slab_floats(const SgGenPlan &P, int64_t n_pairs);
-int sg_generic_run(const SgGenPlan &P, bool bwd, const void *recs, const int32_t *order,
-                   int64_t n_pairs, int64_t pair_offset, int64_t batch_total, const float *params, uint64_t seed,
-                   const float *y_stats, float *s_out, float *slab, int *blocks_out,
-                   hipStream_t stream);
-// fused fast path (sg_fast.hip)
-int sg_fast_supported(const sg_model_t *m, const SgGenPlan &P);
-int64_t sg_fast_slab_floats(const SgGenPlan &P, int64_t n_pairs);
-int sg_fast_needs_ntn(const SgGenPlan &P);
-int sg_fast_run(const sg_model_t *m, const SgGenPlan &P, bool bwd, const void *recs,
-                const int32_t *order, int64_t n_pairs, int64_t pair_offset, int64_t batch_total, const float *params,
-                uint64_t seed, const float *y_stats, float *s_out, float *slab, float *ntn,
-                int *blocks_out, hipStream_t stream, const uint64_t *seed_dev = nullptr,
-                const sg_pair_source_t *src = nullptr, const int32_t *class_start = nullptr,
-                const SgAdamPre *adam_pre = nullptr);
-// fused capacity-32 path (sg_fast32.hip)
-int sg_fast32_supported(const sg_model_t *m, const SgGenPlan &P);
-// graph-store path for Web-sized graphs (sg_web.hip)
-int sg_web_plan_params(const sg_model_t *m, int64_t *n_params);
-int sg_web_lds_ok(const sg_model_t *m);
-int64_t sg_web_ws_bytes(const sg_model_t *m, int64_t chunk, int64_t n_pairs);
-int sg_web_release_aux();
-int sg_web_run(const sg_model_t *m, const sg_csr_store_t *store, const int32_t *pairs,
-               const float *labels, int64_t n_pairs, int64_t pair_offset, int64_t batch_total,
-               const float *params, uint64_t seed, const float *y_stats, int add_label,
-               float *s_out, float *grad_out, float *loss_out, void *workspace, int64_t chunk,
-               bool bwd, hipStream_t st);
-int64_t sg_fast32_slab_floats(const SgGenPlan &P, int64_t n_pairs);
-int64_t sg_fast32_ntn_floats(int64_t n_pairs);
-int sg_fast32_run(const sg_model_t *m, const SgGenPlan &P, bool bwd, const void *recs,
-                  const int32_t *order, int64_t n_pairs, int64_t pair_offset,
-                  int64_t batch_total, const float *params, uint64_t seed, const float *y_stats,
-                  float *s_out, float *slab, float *ntn, int *blocks_out, hipStream_t stream,
-                  const sg_pair_source_t *src = nullptr);
 
 namespace {
 
@@ -568,6 +531,15 @@ int64_t ntn_offset_floats(const PathChoice &c, int64_t n_pairs) {
   return (slab + (int64_t)kReduceStrands * C + 63) & ~(int64_t)63;
 }
 
+// The launch of the chosen path.  The entry points have rejected what a path does not
+// serve (device seed, class table and Adam scalars off path 1, a store source off paths 1
+// and 2) before they get here.
+int run_path(const PathChoice &c, const sg_model_t *m, const SgPairRun &r, int *nblk) {
+  if (c.path == 1) return sg_fast_run(m, c.plan, r, nblk);
+  if (c.path == 2) return sg_fast32_run(m, c.plan, r, nblk);
+  return sg_generic_run(c.plan, r, nblk);
+}
+
 }  // namespace
 
 // ===========================================================================
@@ -763,16 +735,17 @@ static int32_t forward_impl(const sg_model_t *model, const void *records, const 
   PathChoice c = choose_path(model, false);
   if (c.status != SG_OK) return c.status;
   if (class_start && c.path != 1) return SG_ERR_UNSUPPORTED;
-  if (c.path == 1)
-    return sg_fast_run(model, c.plan, false, records, order, n_pairs, pair_offset, n_pairs, params,
-                       seed, nullptr, s_out, nullptr, nullptr, nullptr, (hipStream_t)stream,
-                       nullptr, nullptr, class_start);
-  if (c.path == 2)
-    return sg_fast32_run(model, c.plan, false, records, order, n_pairs, pair_offset, n_pairs,
-                         params, seed, nullptr, s_out, nullptr, nullptr, nullptr,
-                         (hipStream_t)stream);
-  return sg_generic_run(c.plan, false, records, order, n_pairs, pair_offset, n_pairs, params, seed,
-                        nullptr, s_out, nullptr, nullptr, (hipStream_t)stream);
+  SgPairRun r;
+  r.recs = records;
+  r.order = order;
+  r.class_start = class_start;
+  r.n_pairs = r.batch_total = n_pairs;
+  r.pair_offset = pair_offset;
+  r.params = params;
+  r.seed = seed;
+  r.s_out = s_out;
+  r.stream = (hipStream_t)stream;
+  return run_path(c, model, r, nullptr);
 }
 
 int32_t sg_forward_ex(const sg_model_t *model, const void *records, const int32_t *order,
@@ -851,19 +824,26 @@ static int32_t fwd_bwd_impl(const sg_model_t *model, const void *records, const 
     pre_args.b2 = adam->beta2;
     pre_args.wd = adam->weight_decay;
   }
+  SgPairRun r;
+  r.bwd = true;
+  r.recs = records;
+  r.src = src;
+  r.order = order;
+  r.class_start = class_start;
+  r.n_pairs = n_pairs;
+  r.pair_offset = pair_offset;
+  r.batch_total = batch_total;
+  r.params = params;
+  r.seed = seed;
+  r.seed_dev = seed_dev;
+  r.y_stats = y_stats;
+  r.s_out = s_out;
+  r.slab = slab;
+  r.ntn = slab + ntn_offset_floats(c, n_pairs);
+  r.adam_pre = fuse_adam ? &pre_args : nullptr;
+  r.stream = st;
   int nblk = 0;
-  int rc;
-  if (c.path == 1)
-    rc = sg_fast_run(model, c.plan, true, records, order, n_pairs, pair_offset, batch_total,
-                     params, seed, y_stats, s_out, slab, slab + ntn_offset_floats(c, n_pairs),
-                     &nblk, st, seed_dev, src, class_start, fuse_adam ? &pre_args : nullptr);
-  else if (c.path == 2)
-    rc = sg_fast32_run(model, c.plan, true, records, order, n_pairs, pair_offset, batch_total,
-                       params, seed, y_stats, s_out, slab, slab + ntn_offset_floats(c, n_pairs),
-                       &nblk, st, src);
-  else
-    rc = sg_generic_run(c.plan, true, records, order, n_pairs, pair_offset, batch_total, params,
-                        seed, y_stats, s_out, slab, &nblk, st);
+  int rc = run_path(c, model, r, &nblk);
   if (rc != SG_OK) return rc;
   const int add_label = model->loss_mode == SG_LOSS_BROADCAST ? add_label_term : 0;
   if (fuse_adam && nblk <= kOnePassRows) {
@@ -950,12 +930,16 @@ int32_t sg_forward_src(const sg_model_t *model, const sg_pair_source_t *src,
   if (rc != SG_OK) return rc;
   if (n_pairs == 0) return SG_OK;
   if (!params || !s_out) return SG_ERR_ARG;
-  if (c.path == 1)
-    return sg_fast_run(model, c.plan, false, nullptr, order, n_pairs, pair_offset, n_pairs, params,
-                       seed, nullptr, s_out, nullptr, nullptr, nullptr, (hipStream_t)stream,
-                       nullptr, src);
-  return sg_fast32_run(model, c.plan, false, nullptr, order, n_pairs, pair_offset, n_pairs, params,
-                       seed, nullptr, s_out, nullptr, nullptr, nullptr, (hipStream_t)stream, src);
+  SgPairRun r;
+  r.src = src;
+  r.order = order;
+  r.n_pairs = r.batch_total = n_pairs;
+  r.pair_offset = pair_offset;
+  r.params = params;
+  r.seed = seed;
+  r.s_out = s_out;
+  r.stream = (hipStream_t)stream;
+  return run_path(c, model, r, nullptr);
 }
 
 int32_t sg_fwd_bwd_dseed(const sg_model_t *model, const void *records, const int32_t *order,
