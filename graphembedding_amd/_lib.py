@@ -195,6 +195,16 @@ def lib():
     L.sg_score_grid.restype = c_i32
     L.sg_topk_rows.argtypes = [vp, c_i64, c_i64, c_i64, c_i32, c_i32, vp, vp, vp]
     L.sg_topk_rows.restype = c_i32
+    # embed-once training (include/siamese_embed_train.h)
+    L.sg_score_grid_bwd_workspace_bytes.argtypes = [pm, c_i64, c_i64]
+    L.sg_score_grid_bwd_workspace_bytes.restype = c_i64
+    L.sg_score_grid_fwd_bwd.argtypes = [pm, vp, vp, c_i64, c_i64, vp, vp, c_i64, c_i64, vp, c_i32,
+                                        vp, c_i64, vp, vp, vp, vp, vp, vp]
+    L.sg_score_grid_fwd_bwd.restype = c_i32
+    L.sg_embed_bwd_workspace_bytes.argtypes = [pm, c_i64]
+    L.sg_embed_bwd_workspace_bytes.restype = c_i64
+    L.sg_embed_bwd.argtypes = [pm, vp, vp, vp, c_i32, c_i32, vp, c_i64, vp, vp, vp, vp, vp, vp]
+    L.sg_embed_bwd.restype = c_i32
     _lib = L
     return L
 
@@ -218,6 +228,11 @@ EXPORTED_SYMBOLS = ('sg_version', 'sg_record_bytes', 'sg_record_bytes_ex', 'sg_m
 # symbol list of siamese_hip.h)
 EMBED_SYMBOLS = ('sg_embed_dim', 'sg_embed', 'sg_score_grid_workspace_bytes', 'sg_score_grid',
                  'sg_topk_rows')
+
+# the symbols of include/siamese_embed_train.h (embed-once training; their presence is how a
+# caller detects the feature, sg_version() does not change with them)
+EMBED_TRAIN_SYMBOLS = ('sg_score_grid_bwd_workspace_bytes', 'sg_score_grid_fwd_bwd',
+                       'sg_embed_bwd_workspace_bytes', 'sg_embed_bwd')
 
 # class_start entries of sg_pair_order_cls (include/siamese_hip.h SG_FAST_CLASSES_P1)
 FAST_CLASSES_P1 = 5
@@ -502,6 +517,47 @@ def score_grid(m: SgModel, emb_q, emb_db, n_q, n_db, params, apply_final, out, l
     check(lib().sg_score_grid(ctypes.byref(m), _ptr(emb_q), _ptr(emb_db), int(n_q), int(n_db),
                               _ptr(params), int(bool(apply_final)), _ptr(out), int(ld_out),
                               _ptr(workspace), _stream(stream)), 'sg_score_grid')
+
+
+_NO_TRAIN_GRID = ('embed-once training serves models without effective dropout, off the '
+                  'graph-store path{}')
+
+
+def score_grid_bwd_workspace_bytes(m: SgModel, n_q: int, n_db: int) -> int:
+    b = int(lib().sg_score_grid_bwd_workspace_bytes(ctypes.byref(m), int(n_q), int(n_db)))
+    if b < 0:
+        raise SiameseHipError('sg_score_grid_bwd_workspace_bytes: ' + _NO_TRAIN_GRID.format(
+            ', with the NTN head (input_dim <= 31, feature_map_dim <= 16)'))
+    return b
+
+
+def score_grid_fwd_bwd(m: SgModel, emb_q, emb_db, n_q, n_db, params, labels, ld_labels,
+                       batch_total, y_stats, add_label_term, s_out, ld_s, g_emb_q, g_emb_db,
+                       grad_out, loss_out, workspace, stream=None):
+    check(lib().sg_score_grid_fwd_bwd(ctypes.byref(m), _ptr(emb_q), _ptr(emb_db), int(n_q),
+                                      int(n_db), _ptr(params), _ptr(labels), int(ld_labels),
+                                      int(batch_total), _ptr(y_stats), int(bool(add_label_term)),
+                                      _ptr(s_out), int(ld_s), _ptr(g_emb_q), _ptr(g_emb_db),
+                                      _ptr(grad_out), _ptr(loss_out), _ptr(workspace),
+                                      _stream(stream)), 'sg_score_grid_fwd_bwd')
+
+
+def embed_bwd_workspace_bytes(m: SgModel, count: int) -> int:
+    b = int(lib().sg_embed_bwd_workspace_bytes(ctypes.byref(m), int(count)))
+    if b < 0:
+        raise SiameseHipError('sg_embed_bwd_workspace_bytes: ' + _NO_TRAIN_GRID.format(''))
+    return b
+
+
+def embed_bwd(m: SgModel, store_dev, n_max, graph_idx, count, params, g_emb, grad_out, workspace,
+              status=None, stream=None):
+    """sg_embed_bwd over a device dense store (adj, types, n): the node layers' range of
+    grad_out from the embedding gradients g_emb [count][E]."""
+    adj, types, n = store_dev
+    check(lib().sg_embed_bwd(ctypes.byref(m), _ptr(adj), _ptr(types), _ptr(n), int(n.numel()),
+                             int(n_max), _ptr(graph_idx), int(count), _ptr(params), _ptr(g_emb),
+                             _ptr(grad_out), _ptr(status), _ptr(workspace), _stream(stream)),
+          'sg_embed_bwd')
 
 
 def topk_rows(vals, m, n, ld, k, largest, idx_out, val_out=None, stream=None):

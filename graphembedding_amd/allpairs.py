@@ -134,6 +134,43 @@ class AllPairsShard(object):
         return model.balance(b) if balance else b
 
 
+class AllPairsGrid(object):
+    """The all-pairs step embed-once (dropout 0 only): AllPairsShard's counterpart for
+    model.grid_fwd_bwd.  Holds the G x G label matrix and its y_stats on the device; a step
+    embeds the G graphs once, runs the NTN grid forward + backward and one node-stack
+    backward per graph instead of G² pair bodies (include/siamese_embed_train.h).  Same
+    loss and gradient as AllPairsShard's batch at dropout 0, up to fp32 summation order."""
+
+    def __init__(self, gs: GraphSet, labels: np.ndarray, device='cuda'):
+        import torch
+        G = len(gs.graphs)
+        lab = np.ascontiguousarray(np.asarray(labels, np.float32).reshape(G, G))
+        self.store = gs.store
+        self.total = G * G
+        self.labels = torch.from_numpy(lab).to(device)
+        y = lab.reshape(-1).astype(np.float64)
+        ybar = y.mean()
+        self.y_stats = torch.tensor([ybar, 0.5 * ((y - ybar) ** 2).sum()], dtype=torch.float32,
+                                    device=device)
+        self._problem = None
+        self._owner = None
+
+    def problem(self, model):
+        """The model's GridProblem of this grid (built once per model)."""
+        owner = self._owner() if self._owner is not None else None
+        if owner is not model:
+            self._problem = model.grid_problem(self.store, self.labels, y_stats=self.y_stats)
+            self._owner = weakref.ref(model)
+        return self._problem
+
+    def fwd_bwd(self, model, add_label_term: bool = True):
+        """Leaves the gradient / loss_mse in model.grad / model.loss_buf."""
+        model.grid_fwd_bwd(self.problem(model), add_label_term=add_label_term)
+
+    def train_step(self, model, sync: bool = True):
+        return model.grid_train_step(self.problem(model), sync=sync)
+
+
 class AllPairsStream(object):
     """This rank's slice of the all-pairs stream, packed and stepped chunk by chunk.
 

@@ -16,34 +16,7 @@ namespace {
 
 using sgk::f4;
 
-constexpr int kGridMaxD = 31;     // D + 1 <= 32: at most 8 MFMA k-steps
-constexpr int kGridMaxK = 16;     // one 16-column tile
 constexpr int kTopkMax = 64;
-constexpr int64_t kMaxRows = (int64_t)1 << 29;   // launch sizes stay below 2^31 workgroups
-
-// The plan of the model with dropout off and the f32 store (inference mode)
-int embed_plan(const sg_model_t *model, SgGenPlan *P) {
-  if (!model) return SG_ERR_ARG;
-  int64_t wn = 0;
-  if (sg_web_plan_params(model, &wn) == SG_OK && sg_web_lds_ok(model)) return SG_ERR_UNSUPPORTED;
-  sg_model_t m = *model;
-  m.keep_prob = 1.f;   // every threshold 65536: sg_keep is always true
-  m.adj_dtype = SG_DTYPE_F32;
-  return sg_build_plan(&m, P);
-}
-
-int plan_embed_dim(const SgGenPlan &P) {
-  const SgGenLayer &last = P.L[P.nl - 1];
-  return last.Rout * last.dout;
-}
-
-// largest node count the stack takes: the record capacity and the Padding rows (A9)
-int plan_max_nodes(const SgGenPlan &P) {
-  int mx = P.n_max;
-  for (int l = 0; l < P.nl; ++l)
-    if (P.L[l].kind == SG_PADDING && P.L[l].Rout < mx) mx = P.L[l].Rout;
-  return mx;
-}
 
 // ---------------------------------------------------------------------------
 // Embeddings: one wavefront runs gen_forward_nodes on two graphs (the two "sides" of the
@@ -122,34 +95,18 @@ __global__ void __launch_bounds__(256) sg_embed_kernel(SgGenPlan P, EmbedArgs A)
   }
 }
 
-// ---------------------------------------------------------------------------
-// Query tables Q [m][Dp][16], Dp = D + 1 rounded up to the MFMA k-step of 4; rows above D
-// and columns k >= K are zero.
-// ---------------------------------------------------------------------------
-__global__ void __launch_bounds__(256) sg_grid_q_kernel(const float *__restrict__ eq, int64_t m,
-                                                        int D, int K, int Dp,
-                                                        const float *__restrict__ prm, int offW,
-                                                        int offV, int offB,
-                                                        float *__restrict__ Q) {
-  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (t >= m * Dp * 16) return;
-  const int k = (int)(t & 15);
-  const int64_t ib = t >> 4;
-  const int b = (int)(ib % Dp);
-  const float *e = eq + (ib / Dp) * D;
-  float acc = 0.f;
-  if (k < K && b < D) {
-    for (int a = 0; a < D; ++a) acc = fmaf(e[a], prm[offW + (a * D + b) * K + k], acc);
-    acc += prm[offV + k * 2 * D + D + b];
-  } else if (k < K && b == D) {
-    for (int a = 0; a < D; ++a) acc = fmaf(prm[offV + k * 2 * D + a], e[a], acc);
-    if (offB >= 0) acc += prm[offB + k];
-  }
-  Q[t] = acc;
-}
+}  // namespace
+
+// embed_plan, grid_plan, grid_dp and the query tables' sg_grid_q_kernel, shared with
+// sg_embed_train.hip.  Included here, between the embedding kernel and the grid kernel,
+// where the table kernel was defined: the unit's code object keeps its function order.
+#include "sg_embed_plan.h"
+
+namespace {
 
 // ---------------------------------------------------------------------------
-// Score grid.  A workgroup owns 64 database rows (four 16-row tiles) and a range of
+// Score grid over the tables Q [m][Dp][16].  A workgroup owns 64 database rows (four
+// 16-row tiles) and a range of
 // queries; each of its four wavefronts keeps the augmented rows [e_j, 1, 0…] of the four
 // tiles as MFMA A operands in NS = Dp / 4 registers per tile (lane l: row l & 15, k-slot
 // l >> 4) and walks every fourth query of the range.  Per query the B operand is Q_i
@@ -277,16 +234,6 @@ __global__ void __launch_bounds__(256) sg_topk_kernel(const float *__restrict__ 
     }
   }
 }
-
-// the NTN head the grid serves, or an SG_ERR_* code
-int grid_plan(const sg_model_t *model, SgGenPlan *P) {
-  const int rc = embed_plan(model, P);
-  if (rc != SG_OK) return rc;
-  if (P->head_kind != SG_NTN || P->D > kGridMaxD || P->K > kGridMaxK) return SG_ERR_UNSUPPORTED;
-  return SG_OK;
-}
-
-int grid_dp(const SgGenPlan &P) { return (P.D + 1 + 3) & ~3; }
 
 }  // namespace
 

@@ -93,6 +93,32 @@ class Batch:
     src_keep: tuple = ()            # the device tensors src points into (kept alive)
 
 
+@dataclass
+class GridProblem:
+    """An m x n block of pairs for embed-once training (SiameseGCNTNMSE.grid_problem):
+    device tensors only, so a step runs without host work."""
+    store_dev: tuple                # (adj, types, n) of the GraphStore
+    m: int
+    n: int
+    labels: object                  # torch.float32 [m][n]
+    y_stats: object                 # torch.float32 [2] {ȳ, ½Σ(y-ȳ)²}
+    uniq: object                    # torch.int32 [U] distinct store graphs, ascending
+    q_pos: object                   # torch.int64 [m] position of query i in uniq
+    db_pos: object                  # torch.int64 [n] position of database j in uniq
+    identity: bool                  # queries = database = uniq (the all-pairs grid)
+    emb: object                     # [U][E] embeddings
+    g_emb: object                   # [U][E] their gradients (query role + database role)
+    g_q: object                     # [m][E]
+    g_db: object                    # [n][E]
+    status: object                  # torch.int32 [1] device status of sg_embed / sg_embed_bwd
+    ws_grid: object
+    ws_embed: object
+
+    def check(self):
+        """Raise if a kernel reported a bad graph id or node count (synchronises)."""
+        _lib.check(int(self.status.item()), 'embed-once training (device status)')
+
+
 class SiameseGCNTNMSE(object):
     def __init__(self, input_dim, flags=None, device='cuda', n_max=None, params=None):
         f = flags or FLAGS
@@ -556,6 +582,107 @@ class SiameseGCNTNMSE(object):
         val = torch.empty((m, max(int(k), 0)), dtype=torch.float32, device=self.device)
         _lib.topk_rows(s, m, n, n, k, largest, idx, val)
         return idx, val
+
+    # ---- embed-once training (include/siamese_embed_train.h; dropout 0 only) ----
+    def _no_dropout(self, what):
+        if self.flags.dropout != 0:
+            raise _lib.SiameseHipError(
+                '{}: embed-once training needs flags.dropout = 0 (it is {}): the reference '
+                'draws its dropout masks per pair, so with dropout on a graph\'s embedding '
+                'depends on its partner; use fwd_bwd / train_step'.format(what,
+                                                                          self.flags.dropout))
+
+    def grid_problem(self, store: GraphStore, labels, q_idx=None, db_idx=None, y_stats=None):
+        """The device-resident state of an m x n block of pairs (query q_idx[i] as graph 1,
+        database db_idx[j] as graph 2; None = every store graph) with labels [m][n]: the
+        distinct graphs, where each query / database entry sits among them, the labels and
+        their {ȳ, ½Σ(y−ȳ)²} (float64, as AllPairsShard), and every buffer a step needs.
+        Build once, step many times (grid_fwd_bwd / grid_train_step)."""
+        torch = self.torch
+        self._no_web('grid_problem')
+        self._no_dropout('grid_problem')
+        if store.n_max != self.n_max:
+            raise _lib.SiameseHipError('store n_max {} != model n_max {}'.format(store.n_max,
+                                                                                 self.n_max))
+        self.check_node_counts(store.n, 'grid_problem')
+        G = len(store)
+        if G == 0 or int(np.asarray(store.n).min()) < 1:
+            raise _lib.SiameseHipError('grid_problem: every store graph needs at least one node')
+        q = np.arange(G) if q_idx is None else np.asarray(q_idx, np.int64).reshape(-1)
+        db = np.arange(G) if db_idx is None else np.asarray(db_idx, np.int64).reshape(-1)
+        both = np.concatenate([q, db])
+        if both.size and (both.min() < 0 or both.max() >= G):
+            raise _lib.SiameseHipError('grid_problem: graph ids must lie in [0, {})'.format(G))
+        uniq, inv = np.unique(both, return_inverse=True)
+        m, n, dev = int(q.size), int(db.size), self.device
+        lab = torch.as_tensor(labels if torch.is_tensor(labels) else
+                              np.asarray(labels, np.float32), dtype=torch.float32,
+                              device=dev).contiguous()
+        if tuple(lab.shape) != (m, n):
+            raise _lib.SiameseHipError('grid_problem: labels must be [{}][{}]'.format(m, n))
+        if y_stats is None:
+            y64 = lab.double()
+            ybar = y64.mean() if m * n else torch.zeros((), dtype=torch.float64, device=dev)
+            y_stats = torch.stack([ybar, 0.5 * ((y64 - ybar) ** 2).sum()]).float()
+        E, U = self.embed_dim, int(uniq.size)
+        f32 = dict(dtype=torch.float32, device=dev)
+
+        def ws(nbytes):
+            return torch.empty(nbytes // 4 + 1, **f32)
+        return GridProblem(
+            store_dev=store.to_device(dev), m=m, n=n, labels=lab, y_stats=y_stats,
+            uniq=torch.from_numpy(uniq.astype(np.int32)).to(dev),
+            q_pos=torch.from_numpy(inv[:m].astype(np.int64)).to(dev),
+            db_pos=torch.from_numpy(inv[m:].astype(np.int64)).to(dev),
+            identity=bool(m == n == U and np.array_equal(q, uniq) and np.array_equal(db, uniq)),
+            emb=torch.empty((U, E), **f32), g_emb=torch.empty((U, E), **f32),
+            g_q=torch.empty((m, E), **f32), g_db=torch.empty((n, E), **f32),
+            status=torch.zeros(1, dtype=torch.int32, device=dev),
+            ws_grid=ws(_lib.score_grid_bwd_workspace_bytes(self.sg, m, n)),
+            ws_embed=ws(_lib.embed_bwd_workspace_bytes(self.sg, U)))
+
+    def grid_fwd_bwd(self, store, labels=None, q_idx=None, db_idx=None, add_label_term=True,
+                     s_out=None):
+        """fwd_bwd over the m x n block of pairs, embed-once: every distinct graph's node
+        stack runs forward once (sg_embed), the NTN grid runs forward and backward
+        (sg_score_grid_fwd_bwd: loss, the head's gradient, the embeddings' gradients), the
+        query-role and database-role gradients of each graph are summed and go once through
+        its node stack (sg_embed_bwd).  Leaves Σ∂loss_mse/∂θ in self.grad and loss_mse in
+        self.loss_buf[0] exactly where fwd_bwd over the m·n pairs (batch_total = m·n) leaves
+        them, up to fp32 summation order.  store: a GraphStore with labels [m][n], or a
+        grid_problem(...) built once.  s_out: [m][n] pre-activation scores, optional.
+        Needs flags.dropout = 0 and the NTN head the score grid serves."""
+        self._no_dropout('grid_fwd_bwd')
+        gp = store if isinstance(store, GridProblem) else \
+            self.grid_problem(store, labels, q_idx, db_idx)
+        sg, nmax = self.sg, self.n_max
+        U = int(gp.uniq.numel())
+        _lib.embed(sg, gp.store_dev, nmax, gp.uniq, U, self.params, gp.emb, gp.status)
+        eq, edb = (gp.emb, gp.emb) if gp.identity else (gp.emb[gp.q_pos], gp.emb[gp.db_pos])
+        _lib.score_grid_fwd_bwd(sg, eq, edb, gp.m, gp.n, self.params, gp.labels, gp.n,
+                                gp.m * gp.n, gp.y_stats, add_label_term, s_out, gp.n, gp.g_q,
+                                gp.g_db, self.grad, self.loss_buf, gp.ws_grid)
+        if gp.identity:
+            self.torch.add(gp.g_q, gp.g_db, out=gp.g_emb)
+        else:
+            gp.g_emb.zero_()
+            gp.g_emb.index_add_(0, gp.q_pos, gp.g_q)
+            gp.g_emb.index_add_(0, gp.db_pos, gp.g_db)
+        _lib.embed_bwd(sg, gp.store_dev, nmax, gp.uniq, U, self.params, gp.g_emb, self.grad,
+                       gp.ws_embed, gp.status)
+        return gp
+
+    def grid_train_step(self, store, labels=None, q_idx=None, db_idx=None, sync=True):
+        """grid_fwd_bwd followed by Adam: train_step's embed-once counterpart (same loss
+        return: loss_mse + weight decay at the pre-update parameters)."""
+        self.grid_fwd_bwd(store, labels, q_idx, db_idx)
+        if self.grad_hook is not None:
+            self.grad_hook(self)
+        self.apply_adam()
+        self.step_count += 1
+        if not sync:
+            return None
+        return float(self.loss_buf[0].item() + self.reg_buf[0].item())
 
     def flat_params(self) -> np.ndarray:
         return self.params.detach().cpu().numpy()
