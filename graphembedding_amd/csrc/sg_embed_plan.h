@@ -28,11 +28,13 @@ int plan_embed_dim(const SgGenPlan &P) {
   return last.Rout * last.dout;
 }
 
-// largest node count the stack takes: the record capacity and the Padding rows (A9)
+// largest node count the stack takes: the record capacity and the rows of a Padding layer
+// that pads the graph's own rows (A9).  A Padding layer after pooling or after another
+// Padding (rin_fixed >= 0) pads a fixed row count and does not bound the graph.
 int plan_max_nodes(const SgGenPlan &P) {
   int mx = P.n_max;
   for (int l = 0; l < P.nl; ++l)
-    if (P.L[l].kind == SG_PADDING && P.L[l].Rout < mx) mx = P.L[l].Rout;
+    if (P.L[l].kind == SG_PADDING && P.L[l].rin_fixed < 0 && P.L[l].Rout < mx) mx = P.L[l].Rout;
   return mx;
 }
 

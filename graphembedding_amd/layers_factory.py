@@ -98,7 +98,11 @@ def create_layers(flags, input_dim: int) -> List[dict]:
 
 
 def padding_dims(layers: List[dict]):
+    """max_in_dims of the Padding layer that pads the graph's own rows, else None: a Padding
+    layer after Average / Attention pads the single pooled row and bounds no graph."""
     for L in layers:
+        if L['kind'] in ('Average', 'Attention'):
+            return None
         if L['kind'] == 'Padding':
             return L['max_in_dims']
     return None

@@ -198,7 +198,14 @@ class Graph:
 
 
 def _node_forward(spec: OracleSpec, P, g: Graph, side: int, pair: int, seed: int):
-    """Node-level stack + pooling for one graph instance (layers.py:91-227)."""
+    """Node-level stack + pooling for one graph instance (layers.py:91-227).
+
+    A Dense or a Padding layer after Average / Attention takes the pooled vector as one
+    (1, d) row: the ordinary Dense / Padding arithmetic with a single row, which is how the
+    engine's plan (csrc/sg_plan.h, rin_fixed = 1) reads such a stack.  The reference's TF code
+    cannot run these stacks at all (Average returns a rank-1 tensor, layers.py:136-140, and
+    tf.matmul / the rank-2 paddings of layers.py:223-227 need rank 2), so the plan's reading
+    is the definition.  The head still sees a flat vector."""
     x = None          # current tensor (rows x D); None = sparse one-hot X
     rows = g.n
     caches = []
@@ -232,22 +239,29 @@ def _node_forward(spec: OracleSpec, P, g: Graph, side: int, pair: int, seed: int
         elif k == 'Dense':
             W = P[(li, 'weights')]
             b = P.get((li, 'bias'))
+            pooled_in = x.ndim == 1                              # after Average / Attention
+            if pooled_in:
+                x = x.reshape(1, -1)
             m = dropout_mask(seed, pair, side, li, x.size, keep).reshape(x.shape)
             xd = np.where(m, x / keep, 0.0)                      # layers.py:196
             pre = xd @ W
             if b is not None:
                 pre = pre + b
             out = _act(L['act'], pre)
-            caches.append(dict(kind=k, li=li, xd=xd, m=m, keep=keep, pre=pre, out=out, act=L['act']))
+            caches.append(dict(kind=k, li=li, xd=xd, m=m, keep=keep, pre=pre, out=out, act=L['act'],
+                               pooled_in=pooled_in))
             x = out
         elif k == 'Padding':
             P_ = L['max_in_dims']
+            pooled_in = x.ndim == 1                              # after Average / Attention
+            if pooled_in:
+                x = x.reshape(1, -1)
             if x.shape[0] > P_:
                 # tf.pad with a negative padding raises (layers.py:226, quirk A9)
                 raise RuntimeError('Padding: {} rows > max_in_dims {}'.format(x.shape[0], P_))
             out = np.full((P_, x.shape[1]), float(L.get('padding_value', 0)))
             out[:x.shape[0]] = x
-            caches.append(dict(kind=k, li=li, rows=x.shape[0]))
+            caches.append(dict(kind=k, li=li, rows=x.shape[0], pooled_in=pooled_in))
             x = out
         elif k == 'Average':
             caches.append(dict(kind=k, li=li, rows=x.shape[0]))
@@ -293,8 +307,12 @@ def _node_backward(spec: OracleSpec, P, G, g: Graph, caches, gx):
             G[(li, 'weights')] += c['xd'].T @ gpre
             gxd = gpre @ W.T
             gx = np.where(c['m'], gxd / c['keep'], 0.0)
+            if c['pooled_in']:
+                gx = gx.reshape(-1)
         elif k == 'Padding':
             gx = gx[:c['rows']]
+            if c['pooled_in']:
+                gx = gx.reshape(-1)
         elif k == 'Average':
             gx = np.tile(gx / c['rows'], (c['rows'], 1))
         elif k == 'Attention':

@@ -48,12 +48,16 @@ def torch_forward(spec, P, g, side, pair, seed):
                 out = out + P[(li, 'bias')]
             x = _act(L['act'], out)
         elif k == 'Dense':
+            if x.dim() == 1:                 # the pooled vector as one row (csrc/sg_plan.h)
+                x = x.reshape(1, -1)
             m = torch.as_tensor(O.dropout_mask(seed, pair, side, li, x.numel(), keep)).reshape(x.shape)
             out = (x / keep * m) @ P[(li, 'weights')]
             if (li, 'bias') in P:
                 out = out + P[(li, 'bias')]
             x = _act(L['act'], out)
         elif k == 'Padding':
+            if x.dim() == 1:
+                x = x.reshape(1, -1)
             x = torch.nn.functional.pad(x, (0, 0, 0, L['max_in_dims'] - x.shape[0]),
                                         value=float(L['padding_value']))
         elif k == 'Average':
