@@ -46,7 +46,7 @@ int head_offset(const SgGenPlan &P) { return P.head_kind == SG_NTN ? P.offW : P.
 // so the workspace query and the launch agree everywhere)
 // ---------------------------------------------------------------------------
 struct TrainGeo {
-  int64_t ncb, nqc, qb, blocks;   // column blocks of 64, query chunks of qb, workgroups
+  GridSplit split;                // for kTrainGridBlocks workgroups, whatever the device
   int64_t chunk, nch;             // queries per table-adjoint chunk, chunks
   int64_t nT;                     // table-adjoint columns: W, V, bias
   int64_t oQ, ogQ, ogQp, ogdbp, oblk, otab, floats;   // workspace offsets in floats
@@ -56,29 +56,22 @@ int64_t up64(int64_t x) { return (x + 63) & ~(int64_t)63; }
 
 bool train_geo(const SgGenPlan &P, int64_t m, int64_t n, TrainGeo *G) {
   const int64_t Dp = grid_dp(P), D = P.D, K = P.K;
-  G->ncb = (n + 63) / 64;
-  int64_t nqc = (kTrainGridBlocks + G->ncb - 1) / (G->ncb > 0 ? G->ncb : 1);
-  const int64_t max_qc = (m + 3) / 4;
-  nqc = nqc > max_qc ? max_qc : nqc;
-  nqc = nqc < 1 ? 1 : nqc;
-  G->qb = (((m + nqc - 1) / nqc) + 3) & ~(int64_t)3;
-  G->qb = G->qb < 4 ? 4 : G->qb;
-  G->nqc = (m + G->qb - 1) / G->qb;
-  G->blocks = G->ncb * G->nqc;
+  G->split = grid_split(m, n, kTrainGridBlocks);
+  const GridSplit &s = G->split;
   G->chunk = (m + 1023) / 1024 > 64 ? (m + 1023) / 1024 : 64;
   G->nch = (m + G->chunk - 1) / G->chunk;
   G->nT = D * D * K + 2 * D * K + K;
   // the partials of the query tables' gradients dominate: refuse what overflows int64
-  const double est = (double)G->ncb * (double)m * (double)(Dp * 16) +
-                     (double)G->nqc * (double)n * (double)D + 2.0 * (double)m * (double)(Dp * 16) +
-                     (double)G->blocks * kBlkStride + (double)G->nch * (double)G->nT;
-  if (est > 1.0e18 || G->blocks > 0x7FFFFFFF) return false;
+  const double est = (double)s.ncb * (double)m * (double)(Dp * 16) +
+                     (double)s.nqc * (double)n * (double)D + 2.0 * (double)m * (double)(Dp * 16) +
+                     (double)s.blocks * kBlkStride + (double)G->nch * (double)G->nT;
+  if (est > 1.0e18 || s.blocks > 0x7FFFFFFF) return false;
   int64_t o = 0;
   G->oQ = o;    o += up64(m * Dp * 16);
   G->ogQ = o;   o += up64(m * Dp * 16);
-  G->ogQp = o;  o += up64(G->ncb * m * Dp * 16);
-  G->ogdbp = o; o += up64(G->nqc * n * D);
-  G->oblk = o;  o += up64(G->blocks * kBlkStride);
+  G->ogQp = o;  o += up64(s.ncb * m * Dp * 16);
+  G->ogdbp = o; o += up64(s.nqc * n * D);
+  G->oblk = o;  o += up64(s.blocks * kBlkStride);
   G->otab = o;  o += up64(G->nch * G->nT);
   G->floats = o;
   return true;
@@ -106,12 +99,11 @@ bool train_geo(const SgGenPlan &P, int64_t m, int64_t n, TrainGeo *G) {
 // go to the workspace and are summed in a fixed order (sg_sum_rows); gU and the loss go
 // to one partial row per workgroup.  No float atomics.
 // ---------------------------------------------------------------------------
-struct TrainGridArgs {
-  const float *Q, *edb, *U, *labels, *y_stats;
-  int64_t m, n, ld_lab, ld_s, ncb;
-  int D, K, qb;
-  int act, ntn_mode, final_act, loss_mode;
-  float yeta, inv_batch;
+struct TrainGridArgs : GridCommon {
+  const float *labels, *y_stats;
+  int64_t ld_lab, ld_s;
+  int loss_mode;
+  float inv_batch;
   float *s_out, *gQp, *gdbp, *blkp;
 };
 
@@ -126,39 +118,31 @@ __global__ void __launch_bounds__(256) sg_grid_bwd_kernel(TrainGridArgs A) {
   const int g = lane >> 4, c = lane & 15;
   const int64_t cb = (int64_t)blockIdx.x % A.ncb, qc = (int64_t)blockIdx.x / A.ncb;
   const int64_t j0 = cb * 64;
-  const int D = A.D, K = A.K;
-  auto aug = [&](int64_t j, int b) -> float {
-    if (j >= A.n || b > D) return 0.f;
-    return b < D ? A.edb[j * D + b] : 1.f;
-  };
+  const int D = A.D;
   float a[4][NS], aT[4][4][NB];
 #pragma unroll
   for (int t = 0; t < 4; ++t) {
 #pragma unroll
-    for (int s = 0; s < NS; ++s) a[t][s] = aug(j0 + 16 * t + c, 4 * s + g);
+    for (int s = 0; s < NS; ++s) a[t][s] = grid_aug(A, j0 + 16 * t + c, 4 * s + g);
 #pragma unroll
     for (int r = 0; r < 4; ++r)
 #pragma unroll
-      for (int bt = 0; bt < NB; ++bt) aT[t][r][bt] = aug(j0 + 16 * t + 4 * g + r, 16 * bt + c);
+      for (int bt = 0; bt < NB; ++bt)
+        aT[t][r][bt] = grid_aug(A, j0 + 16 * t + 4 * g + r, 16 * bt + c);
   }
-  // column weights in both layouts: k = c (M) and k = 4 g + r (MT).  w: the weight of r_k
-  // in the score (intended U_k; reference, quirk A1: 1, the sum is scaled by ΣU); uw: ∂s/∂r_k
-  float usum = 1.f;
-  if (A.ntn_mode != SG_NTN_INTENDED) {
-    usum = 0.f;
-    for (int k = 0; k < K; ++k) usum += A.U[k];
-  }
-  const bool intended = A.ntn_mode == SG_NTN_INTENDED;
-  const bool kmask = c < K;
-  const float uw = kmask ? (intended ? A.U[c] : usum) : 0.f;
+  // column weights (grid_col) in both layouts: k = c (M) and k = 4 g + r (MT)
+  const float usum = grid_usum(A);
+  const GridCol col = grid_col(A, c, usum);
+  const bool kmask = col.mask;
+  const float uw = col.uw;
   bool kmT[4];
   float wT[4], uwT[4];
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
-    const int k = 4 * g + r;
-    kmT[r] = k < K;
-    wT[r] = kmT[r] ? (intended ? A.U[k] : 1.f) : 0.f;
-    uwT[r] = kmT[r] ? (intended ? A.U[k] : usum) : 0.f;
+    const GridCol cT = grid_col(A, 4 * g + r, usum);
+    kmT[r] = cT.mask;
+    wT[r] = cT.w;
+    uwT[r] = cT.uw;
   }
   const bool broadcast = A.loss_mode == SG_LOSS_BROADCAST;
   const float ybar = broadcast ? A.y_stats[0] : 0.f;
@@ -170,10 +154,8 @@ __global__ void __launch_bounds__(256) sg_grid_bwd_kernel(TrainGridArgs A) {
   float uacc[4] = {0.f, 0.f, 0.f, 0.f}, loss_acc = 0.f;
   const int64_t q1 = (qc + 1) * A.qb < A.m ? (qc + 1) * A.qb : A.m;
   for (int64_t i = qc * A.qb + wave; i < q1; i += 4) {
-    const float *__restrict__ Qi = A.Q + i * (NS * 64);
     float b[NS];
-#pragma unroll
-    for (int s = 0; s < NS; ++s) b[s] = Qi[s * 64 + lane];
+    const float *__restrict__ Qi = grid_load_q<NS>(A, i, lane, b);
     f4 qT[NB];   // Q_i[b = 16 bt + c][k = 4 g + 0..3]
 #pragma unroll
     for (int bt = 0; bt < NB; ++bt) {
@@ -301,11 +283,6 @@ __global__ void __launch_bounds__(256) sg_grid_bwd_kernel(TrainGridArgs A) {
         bred[3][threadIdx.x];
 }
 
-template <int NS>
-void launch_grid_bwd(const TrainGridArgs &A, int64_t blocks, hipStream_t st) {
-  hipLaunchKernelGGL(sg_grid_bwd_kernel<NS>, dim3((unsigned)blocks), dim3(256), 0, st, A);
-}
-
 // dst[c] = Σ_r src[r][c], rows in order (deterministic)
 __global__ void __launch_bounds__(256) sg_sum_rows(const float *__restrict__ src, int64_t rows,
                                                    int64_t cols, float *__restrict__ dst) {
@@ -409,21 +386,16 @@ __global__ void __launch_bounds__(256) sg_grid_head_kernel(HeadArgs A) {
 }
 
 // ---------------------------------------------------------------------------
-// Node-stack backward: sg_embed_kernel's staging (sg_embed.hip) and forward, the output
-// gradients of the two sides seeded from g_emb, gen_backward_nodes into the workgroup's
-// accumulator G[0 .. head offset).  A side that cannot be embedded (bad id, bad node
-// count, the missing partner of an odd tail) runs the other side's graph with a zero seed:
-// the backward is linear in the seed, so it adds exact zeros.
+// Node-stack backward: sg_embed_kernel's staging (stage_graph_pair, sg_embed_plan.h) and
+// forward, the output gradients of the two sides seeded from g_emb, gen_backward_nodes into
+// the workgroup's accumulator G[0 .. head offset).  A side that cannot be embedded (bad id,
+// bad node count, the missing partner of an odd tail) runs the other side's graph with a
+// zero seed: the backward is linear in the seed, so it adds exact zeros.
 // ---------------------------------------------------------------------------
-struct EmbedBwdArgs {
-  const float *sadj;
-  const int32_t *stypes, *sn;
-  int n_graphs, max_nodes, hoff;
-  const int32_t *gidx;
-  int64_t count;
+struct EmbedBwdArgs : StoreArgs {
+  int hoff;
   const float *params, *g_emb;
   float *slab;   // [gridDim.x][hoff]
-  int32_t *status;
 };
 
 __global__ void __launch_bounds__(256) sg_embed_bwd_kernel(SgGenPlan P, EmbedBwdArgs A) {
@@ -434,43 +406,15 @@ __global__ void __launch_bounds__(256) sg_embed_bwd_kernel(SgGenPlan P, EmbedBwd
   float *S = smem + gfl + wave * P.wave_floats;
   for (int i = threadIdx.x; i < gfl; i += blockDim.x) G[i] = 0.f;
   __syncthreads();
-  const int nmax = P.n_max, nn = nmax * nmax;
   const SgGenLayer &last = P.L[P.nl - 1];
   const int E = last.Rout * last.dout;
   const int64_t npair = (A.count + 1) >> 1;
   for (int64_t q = (int64_t)blockIdx.x * nw + wave; q < npair; q += (int64_t)gridDim.x * nw) {
     int g[2], n[2];
-    bool ok[2];
-    for (int s = 0; s < 2; ++s) {
-      const int64_t c = 2 * q + s;
-      g[s] = 0;
-      n[s] = 0;
-      ok[s] = false;
-      if (c >= A.count) continue;
-      const int64_t id = A.gidx ? (int64_t)A.gidx[c] : c;
-      const bool in_store = id >= 0 && id < A.n_graphs;
-      if (in_store) {
-        g[s] = (int)id;
-        n[s] = A.sn[id];
-      }
-      ok[s] = in_store && n[s] >= 1 && n[s] <= A.max_nodes;
-      if (!ok[s] && lane == 0 && A.status)
-        atomicExch(A.status, (int32_t)(in_store ? SG_ERR_SHAPE : SG_ERR_ARG));
-    }
-    if (!ok[0] && !ok[1]) continue;
-    if (!ok[0]) { g[0] = g[1]; n[0] = n[1]; }
-    if (!ok[1]) { g[1] = g[0]; n[1] = n[0]; }
-    float *adj = S + P.l_rec;
-    int *types = (int *)(S + P.l_rec + P.rec_types);
-    for (int w = lane; w < 2 * nn; w += SG_WAVE) {
-      const int s = w / nn, o = w - s * nn;
-      adj[w] = A.sadj[(size_t)g[s] * nn + o];
-    }
-    for (int w = lane; w < 2 * nmax; w += SG_WAVE) {
-      const int s = w / nmax, o = w - s * nmax;
-      types[w] = A.stypes[(size_t)g[s] * nmax + o];
-    }
-    sg_wsync();
+    bool ok[2], have[2];
+    float *adj;
+    int *types;
+    if (!stage_graph_pair(P, A, S, q, lane, g, n, ok, have, adj, types)) continue;
     gen_forward_nodes(P, S, A.params, adj, types, n[0], n[1], 0u, lane);
     float *gcur = S + P.l_g0, *gnext = S + P.l_g1;
     const float *ge = A.g_emb + (size_t)(2 * q) * E;
@@ -484,25 +428,10 @@ __global__ void __launch_bounds__(256) sg_embed_bwd_kernel(SgGenPlan P, EmbedBwd
   for (int i = threadIdx.x; i < A.hoff; i += blockDim.x) dst[i] = G[i];
 }
 
-struct EmbedBwdLaunch {
-  int nw, blocks;
-  size_t lds;
-};
-
-EmbedBwdLaunch embed_bwd_launch(const SgGenPlan &P, int64_t count) {
-  EmbedBwdLaunch L;
-  const size_t gbytes = (size_t)((head_offset(P) + 3) & ~3) * 4u;
-  const size_t wbytes = (size_t)P.wave_floats * 4u;
-  int nw = 4;
-  while (nw > 1 && gbytes + nw * wbytes > 81920u) --nw;
-  L.nw = nw;
-  L.lds = gbytes + nw * wbytes;
-  int per_cu = (int)(163840u / L.lds);
-  per_cu = per_cu < 1 ? 1 : (per_cu > 8 ? 8 : per_cu);
-  const int64_t want = ((count + 1) / 2 + nw - 1) / nw;
-  const int64_t cap = (int64_t)sg_num_cus() * per_cu;
-  L.blocks = (int)(want < cap ? (want > 0 ? want : 1) : cap);
-  return L;
+// the generic kernel's backward shape with the node layers' gradient as the accumulator and
+// one unit per two graphs; the workspace is one slab row per workgroup of this shape
+SgGenLaunch embed_bwd_launch(const SgGenPlan &P, int64_t count) {
+  return sg_gen_launch_shape(P, head_offset(P), (count + 1) / 2);
 }
 
 }  // namespace
@@ -545,48 +474,29 @@ int32_t sg_score_grid_fwd_bwd(const sg_model_t *model, const float *emb_q, const
   float *Q = ws + G.oQ, *gQ = ws + G.ogQ, *gQp = ws + G.ogQp, *gdbp = ws + G.ogdbp;
   float *blkp = ws + G.oblk, *tabp = ws + G.otab;
   const int64_t qelems = m * Dp * 16;
-  hipLaunchKernelGGL(sg_grid_q_kernel, dim3((unsigned)((qelems + 255) / 256)), dim3(256), 0, st,
-                     emb_q, m, D, K, Dp, params, P.offW, P.offV, P.offB, Q);
+  launch_grid_q(P, emb_q, m, params, Q, st);
   TrainGridArgs A;
-  A.Q = Q;
-  A.edb = emb_db;
-  A.U = params + P.offU;
+  fill_grid_common(A, P, Q, emb_db, params, m, n, G.split);
   A.labels = labels;
   A.y_stats = y_stats;
-  A.m = m;
-  A.n = n;
   A.ld_lab = ld_labels;
   A.ld_s = ld_s;
-  A.ncb = G.ncb;
-  A.D = D;
-  A.K = K;
-  A.qb = (int)G.qb;
-  A.act = P.head_act;
-  A.ntn_mode = P.ntn_mode;
-  A.final_act = P.final_act;
   A.loss_mode = P.loss_mode;
-  A.yeta = P.yeta;
   A.inv_batch = batch_total > 0 ? 1.f / (float)batch_total : 0.f;
   A.s_out = s_out;
   A.gQp = gQp;
   A.gdbp = gdbp;
   A.blkp = blkp;
-  switch (Dp / 4) {
-    case 1: launch_grid_bwd<1>(A, G.blocks, st); break;
-    case 2: launch_grid_bwd<2>(A, G.blocks, st); break;
-    case 3: launch_grid_bwd<3>(A, G.blocks, st); break;
-    case 4: launch_grid_bwd<4>(A, G.blocks, st); break;
-    case 5: launch_grid_bwd<5>(A, G.blocks, st); break;
-    case 6: launch_grid_bwd<6>(A, G.blocks, st); break;
-    case 7: launch_grid_bwd<7>(A, G.blocks, st); break;
-    default: launch_grid_bwd<8>(A, G.blocks, st); break;
-  }
+  grid_dispatch_ns(Dp / 4, [&](auto ns) {
+    hipLaunchKernelGGL(sg_grid_bwd_kernel<decltype(ns)::value>, dim3((unsigned)G.split.blocks),
+                       dim3(256), 0, st, A);
+  });
   // fixed-order sums of the partials: gQ over column blocks, g_emb_db over query chunks
   hipLaunchKernelGGL(sg_sum_rows, dim3((unsigned)((qelems + 255) / 256)), dim3(256), 0, st,
-                     (const float *)gQp, G.ncb, qelems, gQ);
+                     (const float *)gQp, G.split.ncb, qelems, gQ);
   const int64_t dbelems = n * D;
   hipLaunchKernelGGL(sg_sum_rows, dim3((unsigned)((dbelems + 255) / 256)), dim3(256), 0, st,
-                     (const float *)gdbp, G.nqc, dbelems, g_emb_db);
+                     (const float *)gdbp, G.split.nqc, dbelems, g_emb_db);
   // table adjoint
   const int nT = (int)G.nT, neb = (nT + 255) / 256;
   hipLaunchKernelGGL(sg_grid_tab_kernel, dim3((unsigned)(G.nch * neb)), dim3(256), 0, st, emb_q,
@@ -598,7 +508,7 @@ int32_t sg_score_grid_fwd_bwd(const sg_model_t *model, const float *emb_q, const
   H.blkp = blkp;
   H.y_stats = y_stats;
   H.nch = G.nch;
-  H.nblk = G.blocks;
+  H.nblk = G.split.blocks;
   H.nT = nT;
   H.nWV = D * D * K + 2 * D * K;
   H.K = K;
@@ -616,8 +526,8 @@ int32_t sg_score_grid_fwd_bwd(const sg_model_t *model, const float *emb_q, const
 int64_t sg_embed_bwd_workspace_bytes(const sg_model_t *model, int64_t count) {
   SgGenPlan P;
   if (count < 0 || train_plan(model, &P, false) != SG_OK) return -1;
-  const EmbedBwdLaunch L = embed_bwd_launch(P, count);
-  if (L.lds > 163840u) return -1;
+  const SgGenLaunch L = embed_bwd_launch(P, count);
+  if (!L.fits()) return -1;
   return (int64_t)L.blocks * head_offset(P) * 4 + 256;
 }
 
@@ -638,25 +548,17 @@ int32_t sg_embed_bwd(const sg_model_t *model, const float *store_adj,
     return hipMemsetAsync(grad_out, 0, (size_t)hoff * 4u, st) == hipSuccess ? SG_OK : SG_ERR_HIP;
   if (!store_adj || !store_types || !store_n || !params || !g_emb || !workspace)
     return SG_ERR_ARG;
-  const EmbedBwdLaunch L = embed_bwd_launch(P, count);
-  if (L.lds > 163840u) return SG_ERR_UNSUPPORTED;
+  const SgGenLaunch L = embed_bwd_launch(P, count);
+  if (!L.fits()) return SG_ERR_UNSUPPORTED;
   EmbedBwdArgs A;
-  A.sadj = store_adj;
-  A.stypes = store_types;
-  A.sn = store_n;
-  A.n_graphs = n_graphs;
-  A.max_nodes = plan_max_nodes(P);
+  fill_store_args(A, P, store_adj, store_types, store_n, n_graphs, graph_idx, count, status_out);
   A.hoff = hoff;
-  A.gidx = graph_idx;
-  A.count = count;
   A.params = params;
   A.g_emb = g_emb;
   A.slab = (float *)workspace;
-  A.status = status_out;
-  if (L.lds > 65536u)
-    (void)hipFuncSetAttribute((const void *)sg_embed_bwd_kernel,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.lds);
-  hipLaunchKernelGGL(sg_embed_bwd_kernel, dim3(L.blocks), dim3(64 * L.nw), L.lds, st, P, A);
+  sg_allow_lds((const void *)sg_embed_bwd_kernel, L.lds_bytes);
+  hipLaunchKernelGGL(sg_embed_bwd_kernel, dim3(L.blocks), dim3(64 * L.waves_per_block),
+                     L.lds_bytes, st, P, A);
   hipLaunchKernelGGL(sg_sum_rows, dim3((unsigned)((hoff + 255) / 256)), dim3(256), 0, st,
                      (const float *)A.slab, (int64_t)L.blocks, (int64_t)hoff, grad_out);
   return hipGetLastError() == hipSuccess ? SG_OK : SG_ERR_HIP;

@@ -191,45 +191,23 @@ __global__ void __launch_bounds__(256) sg_generic_kernel(SgGenPlan P, GenArgs A)
 
 }  // namespace
 
-// Launch configuration of the generic kernel (shared with sg_workspace_bytes).
-struct SgGenLaunch {
-  int waves_per_block;
-  int blocks;
-  size_t lds_bytes;
-};
-
+// Launch shape of the generic kernel (sg_paths.h); the backward's accumulator is the
+// gradient and the loss.  sg_workspace_bytes sizes the slab through sg_generic_slab_floats.
 static SgGenLaunch sg_generic_launch(const SgGenPlan &P, int64_t n_pairs, bool bwd) {
-  SgGenLaunch L;
-  const size_t gbytes = bwd ? (size_t)((P.n_params + 1 + 3) & ~3) * 4u : 0u;
-  const size_t wbytes = (size_t)P.wave_floats * 4u;
-  int nw = 4;
-  while (nw > 1 && gbytes + nw * wbytes > 81920u) --nw;
-  L.waves_per_block = nw;
-  L.lds_bytes = gbytes + nw * wbytes;
-  int per_cu = (int)(163840u / (L.lds_bytes ? L.lds_bytes : 1u));
-  if (per_cu < 1) per_cu = 1;
-  if (per_cu > 8) per_cu = 8;
-  int64_t want = (n_pairs + nw - 1) / nw;
-  int64_t cap = (int64_t)sg_num_cus() * per_cu;
-  L.blocks = (int)(want < cap ? (want > 0 ? want : 1) : cap);
-  return L;
+  return sg_gen_launch_shape(P, bwd ? P.n_params + 1 : 0, n_pairs);
 }
 
-int sg_generic_lds_ok(const SgGenPlan &P, bool bwd) {
-  SgGenLaunch L = sg_generic_launch(P, 1, bwd);
-  return L.lds_bytes <= 163840u;
-}
+int sg_generic_lds_ok(const SgGenPlan &P, bool bwd) { return sg_generic_launch(P, 1, bwd).fits(); }
 
 int64_t sg_generic_slab_floats(const SgGenPlan &P, int64_t n_pairs) {
-  SgGenLaunch L = sg_generic_launch(P, n_pairs, true);
-  return (int64_t)L.blocks * (P.n_params + 1);
+  return (int64_t)sg_generic_launch(P, n_pairs, true).blocks * (P.n_params + 1);
 }
 
 int sg_generic_run(const SgGenPlan &P, const SgPairRun &r, int *blocks_out) {
   const bool bwd = r.bwd;
   const hipStream_t stream = r.stream;
-  SgGenLaunch L = sg_generic_launch(P, r.n_pairs, bwd);
-  if (L.lds_bytes > 163840u) return SG_ERR_UNSUPPORTED;
+  const SgGenLaunch L = sg_generic_launch(P, r.n_pairs, bwd);
+  if (!L.fits()) return SG_ERR_UNSUPPORTED;
   GenArgs A;
   A.recs = (const uint8_t *)r.recs;
   A.order = r.order;
@@ -241,11 +219,8 @@ int sg_generic_run(const SgGenPlan &P, const SgPairRun &r, int *blocks_out) {
   A.y_stats = r.y_stats;
   A.s_out = r.s_out;
   A.slab = r.slab;
-  if (L.lds_bytes > 65536u) {
-    (void)hipFuncSetAttribute(bwd ? (const void *)sg_generic_kernel<true>
-                            : (const void *)sg_generic_kernel<false>,
-                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.lds_bytes);
-  }
+  sg_allow_lds(bwd ? (const void *)sg_generic_kernel<true> : (const void *)sg_generic_kernel<false>,
+               L.lds_bytes);
   if (bwd)
     hipLaunchKernelGGL(sg_generic_kernel<true>, dim3(L.blocks), dim3(64 * L.waves_per_block),
                        L.lds_bytes, stream, P, A);

@@ -39,6 +39,46 @@ struct SgPairRun {
   hipStream_t stream = nullptr;
 };
 
+// ---- launch shape of the kernels that run the generic LDS stack ----
+// sg_generic_kernel (sg_generic.hip), sg_embed_kernel (sg_embed.hip) and sg_embed_bwd_kernel
+// (sg_embed_train.hip): a workgroup holds an optional gradient accumulator and one slice of
+// P.wave_floats per wavefront, and each wavefront walks the call's units (pairs of graphs).
+constexpr size_t kSgGenLdsAim = 81920u;     // 80 KB: four waves shrink until the workgroup fits
+constexpr size_t kSgGenLdsMax = 163840u;    // 160 KB, a CU's LDS: larger workgroups are refused
+constexpr size_t kSgLdsNoAttr = 65536u;     // 64 KB: dynamic LDS above it needs the attribute
+constexpr int kSgGenMaxPerCu = 8;           // workgroups per CU the launch counts on, 1 .. 8
+
+struct SgGenLaunch {
+  int waves_per_block;
+  int blocks;
+  size_t lds_bytes;
+  bool fits() const { return lds_bytes <= kSgGenLdsMax; }
+};
+
+// The shape for an accumulator of acc_floats floats (0: none) and `units` units: no more
+// workgroups than the device holds at once, at least one.
+inline SgGenLaunch sg_gen_launch_shape(const SgGenPlan &P, int acc_floats, int64_t units) {
+  SgGenLaunch L;
+  const size_t gbytes = (size_t)((acc_floats + 3) & ~3) * 4u;
+  const size_t wbytes = (size_t)P.wave_floats * 4u;
+  int nw = 4;
+  while (nw > 1 && gbytes + nw * wbytes > kSgGenLdsAim) --nw;
+  L.waves_per_block = nw;
+  L.lds_bytes = gbytes + nw * wbytes;
+  int per_cu = (int)(kSgGenLdsMax / (L.lds_bytes ? L.lds_bytes : 1u));
+  per_cu = per_cu < 1 ? 1 : (per_cu > kSgGenMaxPerCu ? kSgGenMaxPerCu : per_cu);
+  const int64_t want = (units + nw - 1) / nw;
+  const int64_t cap = (int64_t)sg_num_cus() * per_cu;
+  L.blocks = (int)(want < cap ? (want > 0 ? want : 1) : cap);
+  return L;
+}
+
+// before the launch of a kernel with more dynamic LDS than the default limit
+inline void sg_allow_lds(const void *kernel, size_t lds_bytes) {
+  if (lds_bytes > kSgLdsNoAttr)
+    (void)hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+}
+
 // generic path (sg_generic.hip)
 int sg_generic_lds_ok(const SgGenPlan &P, bool bwd);
 int64_t sg_generic_slab_floats(const SgGenPlan &P, int64_t n_pairs);

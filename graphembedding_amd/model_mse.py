@@ -71,6 +71,28 @@ def splitmix64(x: int) -> int:
     return x ^ (x >> 31)
 
 
+def _distinct_index(g1s: Sequence, g2s: Sequence):
+    """(distinct graphs in order of first appearance, int32 [n, 2] index of every pair's
+    two graphs among them); graphs are told apart by identity."""
+    uniq, index = [], {}
+    idx = np.zeros((len(g1s), 2), np.int32)
+    for k, (a, b) in enumerate(zip(g1s, g2s)):
+        for c, g in enumerate((a, b)):
+            if id(g) not in index:
+                index[id(g)] = len(uniq)
+                uniq.append(g)
+            idx[k, c] = index[id(g)]
+    return uniq, idx
+
+
+def _label_stats(torch, lab, count):
+    """float32 [2] {ȳ, ½Σ(y−ȳ)²} of the label tensor, computed in float64 on its device
+    (ȳ = 0 for an empty set, count = 0)."""
+    y64 = lab.double()
+    ybar = y64.mean() if count else torch.zeros((), dtype=torch.float64, device=lab.device)
+    return torch.stack([ybar, 0.5 * ((y64 - ybar) ** 2).sum()]).float()
+
+
 @dataclass
 class Batch:
     """A packed batch resident on the device (what get_feed_dict returns)."""
@@ -196,6 +218,12 @@ class SiameseGCNTNMSE(object):
                 '{}: graph {} has {} nodes > Padding max_in_dims {} (layers.py:226)'.format(
                     what, k, int(n[k]), self.max_nodes))
 
+    def _check_store_capacity(self, store):
+        """The kernels index a dense store by the model's capacity: its slots must be n_max."""
+        if store.n_max != self.n_max:
+            raise _lib.SiameseHipError('store n_max {} != model n_max {}'.format(store.n_max,
+                                                                                 self.n_max))
+
     # ---- reference API ------------------------------------------------------
     def apply_final_act_np(self, score):
         return self.final_act_np(score)
@@ -253,14 +281,7 @@ class SiameseGCNTNMSE(object):
         torch = self.torch
         if self.is_web:
             return self.make_web_batch(g1s, g2s, labels, pair_offset, batch_total)
-        uniq, index = [], {}
-        idx = np.zeros((len(g1s), 2), np.int32)
-        for k, (a, b) in enumerate(zip(g1s, g2s)):
-            for c, g in enumerate((a, b)):
-                if id(g) not in index:
-                    index[id(g)] = len(uniq)
-                    uniq.append(g)
-                idx[k, c] = index[id(g)]
+        uniq, idx = _distinct_index(g1s, g2s)
         store = GraphStore(uniq, self.n_max, self.input_dim)
         self.check_node_counts(store.n, 'make_batch')
         lab = np.zeros(len(g1s), np.float32) if labels is None else np.asarray(labels, np.float32)
@@ -275,14 +296,7 @@ class SiameseGCNTNMSE(object):
         """ModelGraph pairs → a CSR store of the distinct graphs + pair ids (path 3)."""
         from .web import CsrStore
         torch = self.torch
-        uniq, index = [], {}
-        idx = np.zeros((len(g1s), 2), np.int32)
-        for k, (a, b) in enumerate(zip(g1s, g2s)):
-            for c, g in enumerate((a, b)):
-                if id(g) not in index:
-                    index[id(g)] = len(uniq)
-                    uniq.append(g)
-                idx[k, c] = index[id(g)]
+        uniq, idx = _distinct_index(g1s, g2s)
         store = CsrStore(uniq, self.input_dim, self.n_max)
         lab = np.zeros(len(g1s), np.float32) if labels is None else np.asarray(labels, np.float32)
         gids = np.array([[a.nxgraph.graph.get('gid', -1), b.nxgraph.graph.get('gid', -1)]
@@ -328,11 +342,7 @@ class SiameseGCNTNMSE(object):
         lab = torch.as_tensor(np.asarray(labels, np.float32) if not torch.is_tensor(labels)
                               else labels, dtype=torch.float32, device=self.device)
         if y_stats is None:
-            y64 = lab.double()
-            ybar = y64.mean() if n_pairs else torch.zeros((), dtype=torch.float64,
-                                                          device=self.device)
-            half = 0.5 * ((y64 - ybar) ** 2).sum()
-            y_stats = torch.stack([ybar, half]).float()
+            y_stats = _label_stats(torch, lab, n_pairs)
         return Batch(records=recs, n_pairs=int(n_pairs), labels=lab, y_stats=y_stats,
                      pair_offset=int(pair_offset),
                      batch_total=int(batch_total if batch_total is not None else n_pairs),
@@ -348,9 +358,7 @@ class SiameseGCNTNMSE(object):
         if self.kernel_path not in (1, 2) or self.record_dtype != 'f32':
             raise _lib.SiameseHipError('store-sourced batches need a fused kernel path with '
                                        'f32 records (kernel path {})'.format(self.kernel_path))
-        if store.n_max != self.n_max:
-            raise _lib.SiameseHipError('store n_max {} != model n_max {}'.format(store.n_max,
-                                                                                 self.n_max))
+        self._check_store_capacity(store)
         torch = self.torch
         n_pairs = int(n_pairs)
         self.check_node_counts(store.n, 'batch_from_store')
@@ -534,9 +542,7 @@ class SiameseGCNTNMSE(object):
         this model's n_max.  Dropout is off whatever flags.dropout says."""
         torch = self.torch
         self._no_web('embed')
-        if store.n_max != self.n_max:
-            raise _lib.SiameseHipError('store n_max {} != model n_max {}'.format(store.n_max,
-                                                                                 self.n_max))
+        self._check_store_capacity(store)
         self.check_node_counts(store.n, 'embed')
         idx = None
         count = len(store)
@@ -601,9 +607,7 @@ class SiameseGCNTNMSE(object):
         torch = self.torch
         self._no_web('grid_problem')
         self._no_dropout('grid_problem')
-        if store.n_max != self.n_max:
-            raise _lib.SiameseHipError('store n_max {} != model n_max {}'.format(store.n_max,
-                                                                                 self.n_max))
+        self._check_store_capacity(store)
         self.check_node_counts(store.n, 'grid_problem')
         G = len(store)
         if G == 0 or int(np.asarray(store.n).min()) < 1:
@@ -621,9 +625,7 @@ class SiameseGCNTNMSE(object):
         if tuple(lab.shape) != (m, n):
             raise _lib.SiameseHipError('grid_problem: labels must be [{}][{}]'.format(m, n))
         if y_stats is None:
-            y64 = lab.double()
-            ybar = y64.mean() if m * n else torch.zeros((), dtype=torch.float64, device=dev)
-            y_stats = torch.stack([ybar, 0.5 * ((y64 - ybar) ** 2).sum()]).float()
+            y_stats = _label_stats(torch, lab, m * n)
         E, U = self.embed_dim, int(uniq.size)
         f32 = dict(dtype=torch.float32, device=dev)
 

@@ -94,6 +94,31 @@ def test_grid_fwd_bwd_host_validation(L):
     assert L.sg_score_grid_bwd_workspace_bytes(ok, 1 << 29, 1 << 29) == -1
 
 
+# (D, K, m, n): bytes, as the library returned them when the grid call was first merged.  The
+# call is host arithmetic, independent of the device: the literals pin the query-chunk split
+# (1024 workgroups aimed for) and the workspace layout.
+GRID_BWD_WORKSPACE_BYTES = {
+    (10, 10, 1, 1): 7936,
+    (10, 10, 37, 200): 260864,
+    (31, 16, 5, 65): 123392,
+    (16, 1, 4, 64): 21248,
+    (10, 10, 700, 700): 9630208,
+    (11, 10, 4097, 63): 11302144,
+}
+
+
+def test_grid_bwd_workspace_bytes_are_pinned(L):
+    for (D, K, m, n), want in GRID_BWD_WORKSPACE_BYTES.items():
+        if D == 10:
+            model = lib_model(problem(ntn_stack(D, K, dropout=0.0)))
+        elif D == 31:   # Padding(31) on the capacity-32 records
+            model = lib_model(problem(ntn_stack(D, K, dropout=0.0), n_max=31, n_lo=5, n_hi=30),
+                              n_max=32)
+        else:
+            model = lib_model(problem(ntn_stack(D, K, dropout=0.0), n_max=D), n_max=D)
+        assert L.sg_score_grid_bwd_workspace_bytes(model, m, n) == want, (D, K, m, n)
+
+
 def test_both_calls_refuse_dropout(L):
     """keep_prob = 0.9 with the default stack's dropout=True layers: refused; the same
     stack and keep_prob with every layer's dropout=False has no effective dropout."""
