@@ -8,11 +8,33 @@ gradient and loss within fp32 reassociation error, still bitwise reproducible
 import numpy as np
 import pytest
 
-from _fixtures import AVERAGE_STACK, run_oracle_step, small_problem
+from _fixtures import AVERAGE_STACK, check_grad_per_var, run_oracle_step, small_problem
 
 pytestmark = pytest.mark.gpu
 
 TOL = 1e-4
+# a reassociated fp32 sum, per variable, up to 5000 pairs (test_large_batch_properties)
+SUM_TOL = 1e-5
+# 20011 pairs: 4 x the largest per-variable difference between two runs of the MIXED
+# schedule, one walking the order and one the reversed order (measured 1.85e-7, in
+# 1.weights_0, on an MI355X): what reassociation alone does to this very sum
+SUM_TOL_20011 = 4 * 1.85e-7
+
+
+def _forward_scores(model, batch, seed):
+    """Forward-only scores through the C ABI into a NaN-filled buffer of the test's own
+    (pred_sim_without_act writes into torch.empty, where the caching allocator may hand
+    back a block that still holds an earlier launch's scores: a skipped slot then compares
+    equal).  No slot may be left unwritten."""
+    import torch
+    from graphembedding_amd import _lib
+    s = torch.full((batch.n_pairs,), float('nan'), dtype=torch.float32, device=model.device)
+    _lib.forward(model.sg, batch.records, batch.n_pairs, batch.pair_offset, model.params,
+                 model._seed(seed), s, order=batch.order, class_start=batch.cls)
+    s = s.cpu().numpy()
+    assert not np.isnan(s).any(), '{} of {} slots not scored'.format(int(np.isnan(s).sum()),
+                                                                     batch.n_pairs)
+    return s
 
 
 def _node_counts(prob):
@@ -52,8 +74,8 @@ def test_ordered_step_equals_batch_order(gpu, name):
                          flags_overrides=ov)
     model, batch = prob.make_gpu_model(device=gpu)
     seed = 77
-    s_plain = model.pred_sim_without_act(batch, seed=seed).cpu().numpy()
-    s_out = torch.empty(batch.n_pairs, dtype=torch.float32, device=gpu)
+    s_plain = _forward_scores(model, batch, seed)
+    s_out = torch.full((batch.n_pairs,), float('nan'), dtype=torch.float32, device=gpu)
     model.fwd_bwd(batch, seed=seed, s_out=s_out)
     g_plain = model.grad.cpu().numpy()
     l_plain = float(model.loss_buf[0].item())
@@ -61,14 +83,14 @@ def test_ordered_step_equals_batch_order(gpu, name):
 
     model.balance(batch)
     assert batch.order is not None
-    s_ord = model.pred_sim_without_act(batch, seed=seed).cpu().numpy()
+    s_ord = _forward_scores(model, batch, seed)
     assert np.array_equal(s_ord, s_plain), 'scores must not depend on the processing order'
-    s_out.zero_()
+    s_out.fill_(float('nan'))
     model.fwd_bwd(batch, seed=seed, s_out=s_out)
     assert np.array_equal(s_out.cpu().numpy(), s_bwd_plain)
     g_ord = model.grad.clone()
     scale = max(1.0, float(np.abs(g_plain).max()))
-    assert float(np.abs(g_ord.cpu().numpy() - g_plain).max()) <= 1e-5 * scale
+    check_grad_per_var(g_ord.cpu().numpy(), g_plain, prob.layers, prob.d_in, SUM_TOL)
     assert abs(float(model.loss_buf[0].item()) - l_plain) <= 1e-5 * max(1.0, abs(l_plain))
     model.fwd_bwd(batch, seed=seed)
     if model.kernel_path == 1:
@@ -97,10 +119,10 @@ def test_order_edge_cases(gpu):
     import torch
     prob = small_problem(n_graphs=4, n_pairs=1, seed=3)
     model, batch = prob.make_gpu_model(device=gpu)
-    s1 = model.pred_sim_without_act(batch, seed=5).cpu().numpy()
+    s1 = _forward_scores(model, batch, 5)
     model.balance(batch)
     assert batch.order.cpu().tolist() == [0]
-    assert np.array_equal(model.pred_sim_without_act(batch, seed=5).cpu().numpy(), s1)
+    assert np.array_equal(_forward_scores(model, batch, 5), s1)
 
     prob = small_problem(n_graphs=8, n_pairs=300, seed=4)
     model, batch = prob.make_gpu_model(device=gpu)
@@ -124,7 +146,7 @@ def test_class_schedule_equals_mixed_schedule(gpu, n_pairs):
     seed = 4242
     model.balance(batch, classes=False)
     assert batch.cls is None
-    s_mix = model.pred_sim_without_act(batch, seed=seed).cpu().numpy()
+    s_mix = _forward_scores(model, batch, seed)
     model.fwd_bwd(batch, seed=seed)
     g_mix = model.grad.cpu().numpy()
     l_mix = float(model.loss_buf[0].item())
@@ -135,21 +157,24 @@ def test_class_schedule_equals_mixed_schedule(gpu, n_pairs):
     expect = np.concatenate([[0], np.cumsum(np.bincount(key, minlength=4))])
     assert batch.cls.cpu().tolist() == expect.tolist()
     assert np.array_equal(batch.order.cpu().numpy(), _expected_order(prob, True))
-    s_cls = model.pred_sim_without_act(batch, seed=seed).cpu().numpy()
+    s_cls = _forward_scores(model, batch, seed)
     assert np.array_equal(s_cls, s_mix)
     s_out = torch.full((batch.n_pairs,), float('nan'), dtype=torch.float32, device=gpu)
     model.fwd_bwd(batch, seed=seed, s_out=s_out)
     assert np.array_equal(s_out.cpu().numpy(), s_mix)
     g_cls = model.grad.clone()
-    scale = max(1.0, float(np.abs(g_mix).max()))
-    assert float(np.abs(g_cls.cpu().numpy() - g_mix).max()) <= 1e-5 * scale
+    if n_pairs <= 5000:
+        check_grad_per_var(g_cls.cpu().numpy(), g_mix, prob.layers, prob.d_in, SUM_TOL)
+    else:
+        scale = max(1.0, float(np.abs(g_mix).max()))
+        assert float(np.abs(g_cls.cpu().numpy() - g_mix).max()) <= 1e-5 * scale
+        check_grad_per_var(g_cls.cpu().numpy(), g_mix, prob.layers, prob.d_in, SUM_TOL_20011)
     assert abs(float(model.loss_buf[0].item()) - l_mix) <= 1e-5 * max(1.0, abs(l_mix))
     model.fwd_bwd(batch, seed=seed)
     assert torch.equal(g_cls, model.grad), 'class-schedule fwd_bwd is not bitwise reproducible'
     if n_pairs <= 40:
         ref = run_oracle_step(prob, seed)
         np.testing.assert_allclose(s_cls, ref.s, rtol=TOL, atol=TOL)
-        from _fixtures import check_grad_per_var
         check_grad_per_var(g_cls.cpu().numpy(), ref.grad_mse, prob.layers, prob.d_in, TOL)
 
 
