@@ -32,7 +32,6 @@
 
 #include <list>
 #include <mutex>
-#include <type_traits>
 #include <vector>
 
 #include "sg_mfma.h"
@@ -46,8 +45,6 @@ constexpr int WH1 = 32, WH2 = 16;   // GCN widths of the default stack
 constexpr int WKP = 16;             // NTN K capacity (gm rows, head slab)
 constexpr int WMAXD = 512;          // max Padding / NTN width (LDS budget of one instance)
 constexpr int TB = 128;             // GEMM tile edge
-constexpr int MKS = 20;             // MK LDS tile row stride (16 + 4): conflict-free b128 reads
-constexpr int KMS = TB + 4;         // KM LDS tile row stride
 constexpr int HSLAB = 1 + 2 * WKP;  // head slab row: loss | gU[16] | gb[16]
 constexpr int WSPLIT = 16;   // split-K over pairs of the weight-gradient GEMMs
 constexpr int kUnitChunk = 4096;    // instances per block of the size-class sort (web_icls_*)
@@ -156,12 +153,6 @@ struct WebWs {
 int gcn_blocks_for() { return sg_num_cus(); }
 int head_blocks_for() { return 3 * sg_num_cus(); }
 
-
-// The backward instance kernel reads the dropout keep bits the forward wrote (GcnArgs::masks)
-// instead of re-hashing 13 elements per lane and tile; 0: it re-hashes (A/B)
-// ... and the forward's D2 = dropout(H2) rows (GcnArgs::d2) instead of recomputing Z1 = D1'·W1
-// and the H2 pass, which also drops two of the unit's barriers; 0: it recomputes (A/B)
-
 WebWs web_ws(const WebPlan &W, int64_t chunk) {
   WebWs w;
   if (chunk < 1) chunk = 1;
@@ -183,7 +174,7 @@ WebWs web_ws(const WebPlan &W, int64_t chunk) {
   o = 0;   // slot-relative offsets
   w.X = take(2 * w.Cp * Dp);        // X1 | X2
   w.GX = take(2 * w.Cp * Dp);       // gX1 | gX2
-  // T: the a-tile shares MP[p][k][4] of web_t_kernel_b3<true>, or all of T (f32 path)
+  // T: the a-tile shares MP[p][k][4] of web_t_kernel_b3 / web_t_kernel_kg
   w.T = take(w.Cp * WKP * 4);
   w.GM = take(w.Cp * WKP);
   w.EXT = take(2 * w.Cp);           // int2 per pair
@@ -402,7 +393,7 @@ __global__ void __launch_bounds__(256) web_wprep_h(const float *__restrict__ Wg,
 // Per-instance GCN → Dense → Padding stack (+ backward with recompute).
 // One workgroup per instance (pair, side); node tiles of 16 rows, tile t on wave
 // t % waves (N <= 512: 32 tiles).  The sparse loops read the instance's CSR rows
-// through the caches; LCSR (opt-in) stages them in LDS first.
+// through the caches.
 // ---------------------------------------------------------------------------
 // waves per instance workgroup: 8 forward, 16 backward.
 // The backward wants more than the 128 VGPRs of a 16-wave block and spills ~32 of them
@@ -440,7 +431,8 @@ struct GcnArgs {
   float *slab;       // [gridDim.x][n_gcn] (backward, accumulated)
   uint32_t key, thr0, thr1, thr2, thr4;
   float ik0, ik1, ik2, ik4, padv;
-  int d_in, D, Dp, n_gcn, n_max, max_nnz;
+  int d_in, D, Dp, n_gcn, n_max;
+  int max_nnz;   // the store's, for the record: the kernels size nothing by it
   int ob0, oW1, ob1, oWd, obd;
 };
 
@@ -450,8 +442,7 @@ struct GcnArgs {
 //   sEt [N16] effective type (d_in when dropped / absent),
 //   sZ1 [N16][16]: Z1, then (backward) gZ1,
 //   sD1 [N16][32] (backward): D1' = H1·m1, then gP0,
-//   sScr [8 waves][16][16] (backward): a wave's gS1 tile, re-read as MFMA B operand,
-//   CSR (LCSR): row offsets [N16 + 1], columns [max_nnz], values [max_nnz].
+//   sScr [8 waves][16][16] (backward): a wave's gS1 tile, re-read as MFMA B operand.
 // LDS row strides (words): not multiples of 16, so the random-row b128 gathers of
 // the sparse products spread over the banks (stride 16 puts every row on 4 bank groups)
 constexpr int W0S = 36, ZS = 20, DS = 36;
@@ -469,10 +460,10 @@ constexpr int SCS = 20, SCR = 16 * SCS;
 // place of 32-cycle f32 ones that do not.  0: the f32 MFMAs (A/B)
 
 struct GcnLds {
-  int w0, b0, w1, w1t, b1, wd, w1b, tables, et, gx, z1, d1, scr, rp, col, val, total;
+  int w0, b0, w1, w1t, b1, wd, w1b, tables, et, gx, z1, d1, scr, total;
 };
 
-__host__ __device__ inline GcnLds gcn_lds(int d_in, int n16, int max_nnz, bool bwd, bool lcsr) {
+__host__ __device__ inline GcnLds gcn_lds(int d_in, int n16, bool bwd) {
   GcnLds L;
   int o = 0;
   L.w0 = o; o += (d_in + 1) * W0S;
@@ -490,21 +481,17 @@ __host__ __device__ inline GcnLds gcn_lds(int d_in, int n16, int max_nnz, bool b
   L.z1 = o; o += n16 * ZS;
   L.d1 = o; if (bwd) o += n16 * DS;
   L.scr = o; if (bwd) o += gcn_gw(true) * SCR;
-  L.rp = o; if (lcsr) o += (n16 + 4) & ~3;
-  L.col = o; if (lcsr) o += ((max_nnz + 1) / 2 + 3) & ~3;   // u16 columns
-  L.val = o; if (lcsr) o += (max_nnz + 3) & ~3;
   L.total = o;
   return L;
 }
-
 
 // Σ_e val[e] · f(col[e]) over one CSR row: four neighbours' loads in flight at a time,
 // then a tail of a pair and a single.  (Measured and dropped on C5, profiles/r03_c5ab/: w
 // entries per branch-free step with indices past the row clamped, w = 4 2.97 and w = 8 2.65
 // against 3.88 M pairs/s; the padded entries' LDS gathers cost more than the round trips
 // they save.)  The CSR row extents of a lane's rows are loaded once per unit.
-template <typename CT, typename F>
-__device__ __forceinline__ void csr_row(const CT *__restrict__ col, const float *__restrict__ val,
+template <typename F>
+__device__ __forceinline__ void csr_row(const int *__restrict__ col, const float *__restrict__ val,
                                         int e0, int e1, F f) {
   int e = e0;
   for (; e + 4 <= e1; e += 4) {
@@ -549,23 +536,19 @@ __device__ __forceinline__ bool web_fkeep(uint32_t pk, uint32_t layer, uint32_t 
   return sg_keep(pk, layer, side, e, thr);
 }
 
-template <bool BWD, int NTB, bool LCSR>
+template <bool BWD, int NTB>
 __global__ void __launch_bounds__(64 * gcn_gw(BWD)) web_gcn_kernel(GcnArgs A) {
-  using ColT = typename std::conditional<LCSR, uint16_t, int>::type;
   constexpr int GW_ = gcn_gw(BWD), NT = 64 * GW_, GCN_TPW = (32 + GW_ - 1) / GW_;
   extern __shared__ __attribute__((aligned(16))) float sm[];
   const int tid = threadIdx.x, l = tid & 63, w = tid >> 6;
   const int i = l & 15, g = l >> 4;
   const int d_in = A.d_in;
   const int n16max = (A.n_max + 15) & ~15;
-  const GcnLds L = gcn_lds(d_in, n16max, A.max_nnz, BWD, LCSR);
+  const GcnLds L = gcn_lds(d_in, n16max, BWD);
   float *sW0 = sm + L.w0, *sb0 = sm + L.b0, *sW1 = sm + L.w1, *sW1T = sm + L.w1t;
   float *sb1 = sm + L.b1, *sWd = sm + L.wd;
   int *sEt = (int *)(sm + L.et);
   float *sZ1 = sm + L.z1, *sD1 = sm + L.d1, *scr = sm + L.scr + w * SCR;
-  int *sRp = (int *)(sm + L.rp);
-  uint16_t *sCol = (uint16_t *)(sm + L.col);
-  float *sVal = sm + L.val;
   const float *prm = A.params;
   for (int x = tid; x < (d_in + 1) * WH1; x += NT)
     sW0[(x / WH1) * W0S + x % WH1] = x < d_in * WH1 ? prm[x] * A.ik0 : 0.f;
@@ -612,8 +595,8 @@ __global__ void __launch_bounds__(64 * gcn_gw(BWD)) web_gcn_kernel(GcnArgs A) {
   const int ni = (int)n_inst;
   const int32_t *const isorted = A.isorted;
   const int4 *const ginst = A.inst;
-  const int32_t *const grow_ptr = A.row_ptr, *const gtypes = A.types, *const gcol = A.col;
-  const float *const gval = A.val, *const gGX = A.GX;
+  const int32_t *const gtypes = A.types;
+  const float *const gGX = A.GX;
   const int64_t gCp = A.Cp;
   const int gDp = A.Dp;
   const int32_t *const icls = A.icls;
@@ -634,23 +617,13 @@ __global__ void __launch_bounds__(64 * gcn_gw(BWD)) web_gcn_kernel(GcnArgs A) {
   // its (o, N, eb, nnz) at the top of the iteration, its rows after the first phase.
   // Every thread serves its own instance: node lt = its thread index in the instance's
   // share of the block (NT / gsz threads).
-  constexpr int KM = LCSR ? 4096 / NT : 1;   // CSR entries per thread (LCSR: nnz <= 4096)
-  int pr_rp = 0, pr_ty = 0, pr_col[KM];
-  float pr_val[KM], pr_gx = 0.f;
+  int pr_ty = 0;
+  float pr_gx = 0.f;
   auto load_rows = [&](int64_t q, int4 in, int lt) __attribute__((always_inline)) {
-    const int o = in.x, N = in.y, eb = in.z, nnz = in.w;
-    pr_rp = lt < N ? grow_ptr[o + lt] - eb : 0;
+    const int o = in.x, N = in.y;
     pr_ty = lt < N ? gtypes[o + lt] : 0;
     if (BWD)
       pr_gx = lt < N ? gGX[((int64_t)(q & 1) * gCp + (q >> 1)) * gDp + lt] : 0.f;
-    if (LCSR) {
-#pragma unroll
-      for (int k = 0; k < KM; ++k) {
-        const int e = tid + k * NT;
-        pr_col[k] = e < nnz ? gcol[eb + e] : 0;
-        pr_val[k] = e < nnz ? gval[eb + e] : 0.f;
-      }
-    }
   };
   const int2 u0_ = unit_q(blockIdx.x);
   int64_t q = u0_.x;
@@ -693,29 +666,13 @@ __global__ void __launch_bounds__(64 * gcn_gw(BWD)) web_gcn_kernel(GcnArgs A) {
       d2v[u] = (use_d2 && n < N) ? *(const f4 *)(A.d2 + ((size_t)q * A.Dp + n) * 16 + 4 * g)
                                  : f4{0.f, 0.f, 0.f, 0.f};
     }
-    const int *rp;
-    const ColT *cl;
-    const float *vl;
     // stage the prefetched rows; effective one-hot column per node (sparse dropout of
     // X, layer 0, e = node: d_in = the zero row of sW0 for dropped and absent nodes)
     if (lt < n16)
       sEtk[lt] = (lt < N && sg_keep(pk, 0, side, lt, A.thr0)) ? pr_ty : d_in;
     if (BWD && lt < n16) sGxk[lt] = pr_gx;
-    if (LCSR) {   // units of one instance only (the host passes no isorted with LCSR)
-      if (tid < N) sRp[tid] = pr_rp;
-      if (tid == 0) sRp[N] = in.w;
-#pragma unroll
-      for (int k = 0; k < KM; ++k) {
-        const int e = tid + k * NT;
-        if (e < in.w) {
-          sCol[e] = (uint16_t)pr_col[k];
-          sVal[e] = pr_val[k];
-        }
-      }
-      rp = sRp; cl = (const ColT *)(const void *)sCol; vl = sVal;
-    } else {
-      rp = A.row_ptr + o; cl = (const ColT *)(const void *)A.col; vl = A.val;
-    }
+    const int *const rp = A.row_ptr + o, *const cl = A.col;
+    const float *const vl = A.val;
     const int2 un_ = unit_q(unit + gridDim.x);
     const int64_t qn = un_.x;
     const int gszn = un_.y;
@@ -1039,82 +996,20 @@ __global__ void __launch_bounds__(64 * gcn_gw(BWD)) web_gcn_kernel(GcnArgs A) {
 }
 
 // ---------------------------------------------------------------------------
-// 128×128 f32 MFMA GEMM tiles (4 waves as 2×2, 64×64 per wave).
-// MK layout: rows m, 16 contraction values + pad (one b128 read per 4 k-steps with
-// the k-step order kk = 4g + s); KM layout: 16 contraction rows × 128 (+4).
-// ---------------------------------------------------------------------------
-struct Tile {
-  f4 c[4][4];
-  __device__ void zero() {
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-#pragma unroll
-      for (int b = 0; b < 4; ++b) c[a][b] = f4{0.f, 0.f, 0.f, 0.f};
-  }
-};
-
-__device__ __forceinline__ void mma_mk_mk(Tile &T, const float *sA, const float *sB, int wm,
-                                          int wn, int i, int g) {
-  float4 a[4], b[4];
-#pragma unroll
-  for (int x = 0; x < 4; ++x) {
-    a[x] = *(const float4 *)(sA + (wm * 64 + x * 16 + i) * MKS + 4 * g);
-    b[x] = *(const float4 *)(sB + (wn * 64 + x * 16 + i) * MKS + 4 * g);
-  }
-#pragma unroll
-  for (int s = 0; s < 4; ++s)
-#pragma unroll
-    for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-      for (int ni = 0; ni < 4; ++ni) {
-        const float av = s == 0 ? a[mi].x : s == 1 ? a[mi].y : s == 2 ? a[mi].z : a[mi].w;
-        const float bv = s == 0 ? b[ni].x : s == 1 ? b[ni].y : s == 2 ? b[ni].z : b[ni].w;
-        T.c[mi][ni] = mfma4(av, bv, T.c[mi][ni]);
-      }
-}
-
-__device__ __forceinline__ void mma_km_km(Tile &T, const float *sA, const float *sB, int wm,
-                                          int wn, int i, int g) {
-#pragma unroll
-  for (int s = 0; s < 4; ++s) {
-    float a[4], b[4];
-#pragma unroll
-    for (int x = 0; x < 4; ++x) {
-      a[x] = sA[(4 * g + s) * KMS + wm * 64 + x * 16 + i];
-      b[x] = sB[(4 * g + s) * KMS + wn * 64 + x * 16 + i];
-    }
-#pragma unroll
-    for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-      for (int ni = 0; ni < 4; ++ni) T.c[mi][ni] = mfma4(a[mi], b[ni], T.c[mi][ni]);
-  }
-}
-
-// ---- T on bf16 MFMAs: both operands are split on the
+// NTN GEMMs: 128×128 tiles on bf16 MFMAs (4 waves as 2×2, 64×64 per wave; the grid is
+// (pair block, tile, k)).  Both operands are split on the
 // fly into three bf16 parts (x = h + m + l, sgk::split3: |x - h - m - l| < 2^-21 |x|)
 // and T accumulates hh + hm + mh + hl + lh + mm in f32 on v_mfma_f32_16x16x32_bf16:
 // 6 MFMAs of 16 cycles per 32-deep product instead of 8 f32 MFMAs of 32 cycles.
 // LDS: [part][128 rows][40 bf16] per operand (80-byte rows: the b128 fragment reads
 // of 8 consecutive rows fall on distinct banks), 60 KiB; 32-deep contraction chunks,
 // the next chunk's f32 operands prefetched into registers during the MFMAs.
+// (Measured and dropped, profiles/r03_c5ab/gemm_*: a 1-D grid where the column tiles of pair
+// block pb (and, for T, each k, slowest) run on blocks L ≡ pb (mod 8), which the dispatcher
+// deals to one XCD, so that the pair block's x rows would come into that XCD's L2 once for
+// all its tiles: 3.82-3.84 against 4.21-4.22 M pairs/s on C5.)
+// ---------------------------------------------------------------------------
 constexpr int B3K = 32, B3S = 40;   // contraction chunk, LDS row stride (bf16)
-
-// Block order of the pair-block GEMMs.  (Measured and dropped: a 1-D grid where the NT column
-// tiles of pair block pb (and, for T, each k, slowest) run on blocks L ≡ pb (mod 8), which
-// the dispatcher deals to one XCD, so that the pair block's x rows would come into that
-// XCD's L2 once for all its tiles.  Measured 3.82-3.84 against 4.21-4.22 M pairs/s on C5
-// (profiles/r03_c5ab/gemm_*).)  The grid is (pair block, tile, k).
-__device__ __forceinline__ void web_pb_tile(int NT, int G8, int &pb, int &tile, int &kk) {
-  pb = (int)blockIdx.x;
-  tile = (int)blockIdx.y;
-  kk = (int)blockIdx.z;
-}
-static dim3 web_pb_grid(int64_t nblk, int NT, int K) {
-  return dim3((unsigned)nblk, (unsigned)NT, (unsigned)K);
-}
-// gX1 / gX2 GEMMs: the contraction runs over (32-deep chunk, k) with k inner, so a chunk's
-// x rows are loaded once and rescaled by gm[p][k] for each k (k outer, the chunk reloaded
-// per k, measured 4.19-4.20 against 4.21-4.22 M pairs/s on C5)
 constexpr int B3PART = TB * B3S;    // bf16 per part plane
 
 __device__ __forceinline__ void b3_split_store(uint16_t *plane, int r, int c, float4 x) {
@@ -1127,10 +1022,24 @@ __device__ __forceinline__ void b3_split_store(uint16_t *plane, int r, int c, fl
   *(uint2 *)(plane + 2 * B3PART + o) = uint2{l01, l23};
 }
 
-// MFUSE: instead of T, write the tile's share of the bilinear term,
+// The split-bf16 product of one 16×16 tile over a 32-deep chunk: the six leading terms of
+// (ah + am + al)(bh + bm + bl), smallest first.  Every NTN GEMM below accumulates through
+// this one order, which the bitwise tests rest on (web_t_kernel_kg ≡ web_t_kernel_b3,
+// pipelined ≡ serial).  The fragments come by value: by reference the kernels compiled to
+// other code (profiles/r10_web_shared/README.md, as for a wrapper of the loads around it).
+__device__ __forceinline__ void b3_mma6(f4 &c, uint4 ah, uint4 am, uint4 al, uint4 bh, uint4 bm,
+                                        uint4 bl) {
+  c = sgk::mfbf(al, bh, c);
+  c = sgk::mfbf(ah, bl, c);
+  c = sgk::mfbf(am, bm, c);
+  c = sgk::mfbf(am, bh, c);
+  c = sgk::mfbf(ah, bm, c);
+  c = sgk::mfbf(ah, bh, c);
+}
+
+// T as the tiles' shares of the bilinear term, one k per block (SG_WEB_TKG=0):
 // MP[p][k][a-tile] = Σ_{a in the tile} x1[p][a] T[p][k][a] (T itself never reaches memory:
-// the head sums the a-tiles, and gx1's T term is a GEMM of its own, web_gx1_kernel_b3)
-template <bool MFUSE>
+// the head sums the a-tiles, and gx1's T term is a GEMM of its own, web_gx_kernel_b3)
 __global__ void __launch_bounds__(256) web_t_kernel_b3(const float *__restrict__ X2,
                                                        const float *__restrict__ Wg,
                                                        const int2 *__restrict__ ext128, int64_t n,
@@ -1138,8 +1047,7 @@ __global__ void __launch_bounds__(256) web_t_kernel_b3(const float *__restrict__
                                                        const float *__restrict__ X1) {
   __shared__ __attribute__((aligned(16))) uint16_t sA[3 * B3PART], sB[3 * B3PART];
   __shared__ float mred[2][TB];
-  int pbk, at, k;
-  web_pb_tile(Dp / TB, (int)((n + TB * 8 - 1) / (TB * 8)), pbk, at, k);
+  const int pbk = (int)blockIdx.x, at = (int)blockIdx.y, k = (int)blockIdx.z;
   if ((int64_t)pbk * TB >= n) return;
   const int64_t p0 = (int64_t)pbk * TB;
   const int a0 = at * TB;
@@ -1184,51 +1092,31 @@ __global__ void __launch_bounds__(256) web_t_kernel_b3(const float *__restrict__
         const int ob = (wn * 64 + ni * 16 + i) * B3S + 8 * g;
         const uint4 bh = *(const uint4 *)(sB + ob), bm = *(const uint4 *)(sB + B3PART + ob),
                     bl = *(const uint4 *)(sB + 2 * B3PART + ob);
-        f4 c = acc[mi][ni];
-        c = sgk::mfbf(al, bh, c);
-        c = sgk::mfbf(ah, bl, c);
-        c = sgk::mfbf(am, bm, c);
-        c = sgk::mfbf(am, bh, c);
-        c = sgk::mfbf(ah, bm, c);
-        c = sgk::mfbf(ah, bh, c);
-        acc[mi][ni] = c;
+        b3_mma6(acc[mi][ni], ah, am, al, bh, bm, bl);
       }
     }
     __syncthreads();
   }
-  if (MFUSE) {
-    // lane (i, g): rows 4g + r of each 16-row group, columns 16 ni + i of the wave's half
-#pragma unroll
-    for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int pl = wm * 64 + mi * 16 + 4 * g + r;
-        const float *x1 = X1 + (p0 + pl) * Dp + a0 + wn * 64 + i;
-        float part = 0.f;
-#pragma unroll
-        for (int ni = 0; ni < 4; ++ni) part = fmaf(x1[ni * 16], acc[mi][ni][r], part);
-        part = sgk::row_sum16(part);
-        if (i == 0) mred[wn][pl] = part;
-      }
-    __syncthreads();
-    if (tid < TB && p0 + tid < n)
-      Tout[((p0 + tid) * WKP + k) * 4 + at] = mred[0][tid] + mred[1][tid];
-    return;
-  }
+  // lane (i, g): rows 4g + r of each 16-row group, columns 16 ni + i of the wave's half
 #pragma unroll
   for (int mi = 0; mi < 4; ++mi)
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      const int64_t p = p0 + wm * 64 + mi * 16 + 4 * g + r;
-      if (p >= n) continue;
-      float *dst = Tout + ((size_t)p * K + k) * Dp + a0 + wn * 64 + i;
+      const int pl = wm * 64 + mi * 16 + 4 * g + r;
+      const float *x1 = X1 + (p0 + pl) * Dp + a0 + wn * 64 + i;
+      float part = 0.f;
 #pragma unroll
-      for (int ni = 0; ni < 4; ++ni) dst[ni * 16] = acc[mi][ni][r];
+      for (int ni = 0; ni < 4; ++ni) part = fmaf(x1[ni * 16], acc[mi][ni][r], part);
+      part = sgk::row_sum16(part);
+      if (i == 0) mred[wn][pl] = part;
     }
+  __syncthreads();
+  if (tid < TB && p0 + tid < n)
+    Tout[((p0 + tid) * WKP + k) * 4 + at] = mred[0][tid] + mred[1][tid];
 }
 
-// ---- T with TKG feature maps k per block (round 4; SG_WEB_TKG=0 at run time: web_t_kernel_b3): web_t_kernel_b3
-// re-fetched a pair block's x2 rows for each of its K x (a-tiles) tiles (18.45 GB per
+// ---- T with TKG feature maps k per block (round 4; SG_WEB_TKG=0 at run time:
+// web_t_kernel_b3), which re-fetched a pair block's x2 rows for each of its K x (a-tiles) tiles (18.45 GB per
 // 524,288-pair chunk against ≈0.5 GB of x rows, rocprof FETCH_SIZE).  Here one 8-wave block
 // stages the x2 chunk once for TKG = 4 feature maps k (the B operands of the four W[k]
 // planes beside it: 150 KB of LDS, one block per CU), so x2 is fetched ceil(K / 4) times per
@@ -1290,42 +1178,33 @@ __global__ void __launch_bounds__(512) web_t_kernel_kg(const float *__restrict__
     // accumulators of two k and the next chunk's loads, would spill)
 #pragma unroll
     for (int mh = 0; mh < 2; ++mh) {
-    uint4 ah[2], am[2], al[2];
+      uint4 ah[2], am[2], al[2];
 #pragma unroll
-    for (int m2 = 0; m2 < 2; ++m2) {
-      const int oa = (wm * 64 + (2 * mh + m2) * 16 + i) * B3S + 8 * g;
-      ah[m2] = *(const uint4 *)(sA + oa);
-      am[m2] = *(const uint4 *)(sA + B3PART + oa);
-      al[m2] = *(const uint4 *)(sA + 2 * B3PART + oa);
-    }
+      for (int m2 = 0; m2 < 2; ++m2) {
+        const int oa = (wm * 64 + (2 * mh + m2) * 16 + i) * B3S + 8 * g;
+        ah[m2] = *(const uint4 *)(sA + oa);
+        am[m2] = *(const uint4 *)(sA + B3PART + oa);
+        al[m2] = *(const uint4 *)(sA + 2 * B3PART + oa);
+      }
 #pragma unroll
-    for (int kx = 0; kx < 2; ++kx) {
-      const int kk = 2 * wk + kx;
-      if (kk >= nk) continue;
-      const uint16_t *sb = sB[kk];
+      for (int kx = 0; kx < 2; ++kx) {
+        const int kk = 2 * wk + kx;
+        if (kk >= nk) continue;
+        const uint16_t *sb = sB[kk];
 #pragma unroll
-      for (int ni = 0; ni < 4; ++ni) {
-        const int ob = (wn * 64 + ni * 16 + i) * B3S + 8 * g;
-        const uint4 bh = *(const uint4 *)(sb + ob), bm = *(const uint4 *)(sb + B3PART + ob),
-                    bl = *(const uint4 *)(sb + 2 * B3PART + ob);
+        for (int ni = 0; ni < 4; ++ni) {
+          const int ob = (wn * 64 + ni * 16 + i) * B3S + 8 * g;
+          const uint4 bh = *(const uint4 *)(sb + ob), bm = *(const uint4 *)(sb + B3PART + ob),
+                      bl = *(const uint4 *)(sb + 2 * B3PART + ob);
 #pragma unroll
-        for (int m2 = 0; m2 < 2; ++m2) {
-          const int mi = 2 * mh + m2;
-          f4 c = acc[kx][mi][ni];
-          c = sgk::mfbf(al[m2], bh, c);
-          c = sgk::mfbf(ah[m2], bl, c);
-          c = sgk::mfbf(am[m2], bm, c);
-          c = sgk::mfbf(am[m2], bh, c);
-          c = sgk::mfbf(ah[m2], bm, c);
-          c = sgk::mfbf(ah[m2], bh, c);
-          acc[kx][mi][ni] = c;
+          for (int m2 = 0; m2 < 2; ++m2)
+            b3_mma6(acc[kx][2 * mh + m2][ni], ah[m2], am[m2], al[m2], bh, bm, bl);
         }
       }
     }
-    }
     __syncthreads();
   }
-  // the tile's share of the bilinear term per k, as web_t_kernel_b3<true>
+  // the tile's share of the bilinear term per k, as web_t_kernel_b3
 #pragma unroll
   for (int kx = 0; kx < 2; ++kx) {
     const int kk = 2 * wk + kx;
@@ -1351,35 +1230,41 @@ __global__ void __launch_bounds__(512) web_t_kernel_kg(const float *__restrict__
   }
 }
 
-// ---- gX2 on bf16 MFMAs (as web_t_kernel_b3): A = gm[p][k] x1[p][a] scaled while
-// staging, B = Wh[k][b][a]; 32-deep chunks of a for each k ----
-__global__ void __launch_bounds__(256) web_gx2_kernel_b3(const float *__restrict__ X1,
-                                                         const float *__restrict__ GM,
-                                                         const float *__restrict__ Wh,
-                                                         const int2 *__restrict__ ext128,
-                                                         int64_t n, int Dp, int K,
-                                                         float *__restrict__ GX2) {
+// ---- the W terms of gX1 and gX2 as GEMMs (T is never stored, so gX1's is one too):
+//   gX1[p][a] += Σ_{k,b} gm[p][k] x2[p][b] W[a][b][k]   (Xc = X2, Wt = Wg[k][a][b])
+//   gX2[p][b] += Σ_{k,a} gm[p][k] x1[p][a] W[a][b][k]   (SIDE2: Xc = X1, Wt = Wh[k][b][a])
+// A = gm·xc scaled while staging, B = Wt's rows of the output tile.  The contraction runs
+// over (32-deep chunk, k) with k inner, so a chunk's x rows are loaded once and rescaled by
+// gm[p][k] for each k (k outer, the chunk reloaded per k, measured 4.19-4.20 against
+// 4.21-4.22 M pairs/s on C5).  The output side's extent bounds the tile, the other side's the
+// contraction ----
+template <bool SIDE2>
+__global__ void __launch_bounds__(256) web_gx_kernel_b3(const float *__restrict__ Xc,
+                                                        const float *__restrict__ GM,
+                                                        const float *__restrict__ Wt,
+                                                        const int2 *__restrict__ ext128,
+                                                        int64_t n, int Dp, int K,
+                                                        float *__restrict__ GXout) {
   __shared__ __attribute__((aligned(16))) uint16_t sA[3 * B3PART], sB[3 * B3PART];
-  int pb, bt, kk_;
-  web_pb_tile(Dp / TB, (int)((n + TB * 8 - 1) / (TB * 8)), pb, bt, kk_);
+  const int pb = (int)blockIdx.x, ot = (int)blockIdx.y;
   if ((int64_t)pb * TB >= n) return;
   const int64_t p0 = (int64_t)pb * TB;
-  const int b0 = bt * TB;
+  const int o0 = ot * TB;
   const int2 e = ext128[pb];
-  if (b0 >= e.y) return;
-  const int na = (e.x + B3K - 1) / B3K * B3K;
+  if (o0 >= (SIDE2 ? e.y : e.x)) return;
+  const int nc = ((SIDE2 ? e.x : e.y) + B3K - 1) / B3K * B3K;
   const int tid = threadIdx.x, l = tid & 63, w = tid >> 6, i = l & 15, g = l >> 4;
   const int wm = w >> 1, wn = w & 1;
   float4 ra[4], rb[4];
   float gmr[4];
-  auto load = [&](int k, int a0, bool xload) {
+  auto load = [&](int k, int c0, bool xload) {
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       const int q = tid + 256 * u, r = q >> 3, c = (q & 7) * 4;
       const int64_t p = p0 + r;
       gmr[u] = p < n ? GM[p * WKP + k] : 0.f;
-      if (xload) ra[u] = *(const float4 *)(X1 + p * Dp + a0 + c);
-      rb[u] = *(const float4 *)(Wh + ((size_t)k * Dp + b0 + r) * Dp + a0 + c);
+      if (xload) ra[u] = *(const float4 *)(Xc + p * Dp + c0 + c);
+      rb[u] = *(const float4 *)(Wt + ((size_t)k * Dp + o0 + r) * Dp + c0 + c);
     }
   };
   f4 acc[4][4];
@@ -1387,7 +1272,7 @@ __global__ void __launch_bounds__(256) web_gx2_kernel_b3(const float *__restrict
   for (int mi = 0; mi < 4; ++mi)
 #pragma unroll
     for (int ni = 0; ni < 4; ++ni) acc[mi][ni] = f4{0.f, 0.f, 0.f, 0.f};
-  const int steps = na / B3K, total = K * steps;
+  const int steps = nc / B3K, total = K * steps;
   if (total > 0) load(0, 0, true);
   for (int st = 0; st < total; ++st) {
 #pragma unroll
@@ -1412,14 +1297,7 @@ __global__ void __launch_bounds__(256) web_gx2_kernel_b3(const float *__restrict
         const int ob = (wn * 64 + ni * 16 + i) * B3S + 8 * g;
         const uint4 bh = *(const uint4 *)(sB + ob), bm = *(const uint4 *)(sB + B3PART + ob),
                     bl = *(const uint4 *)(sB + 2 * B3PART + ob);
-        f4 c = acc[mi][ni];
-        c = sgk::mfbf(al, bh, c);
-        c = sgk::mfbf(ah, bl, c);
-        c = sgk::mfbf(am, bm, c);
-        c = sgk::mfbf(am, bh, c);
-        c = sgk::mfbf(ah, bm, c);
-        c = sgk::mfbf(ah, bh, c);
-        acc[mi][ni] = c;
+        b3_mma6(acc[mi][ni], ah, am, al, bh, bm, bl);
       }
     }
     __syncthreads();
@@ -1430,93 +1308,7 @@ __global__ void __launch_bounds__(256) web_gx2_kernel_b3(const float *__restrict
     for (int r = 0; r < 4; ++r) {
       const int64_t p = p0 + wm * 64 + mi * 16 + 4 * g + r;
       if (p >= n) continue;
-      float *dst = GX2 + p * Dp + b0 + wn * 64 + i;
-#pragma unroll
-      for (int ni = 0; ni < 4; ++ni) dst[ni * 16] += acc[mi][ni][r];
-    }
-}
-
-// ---- the T term of gX1 as a GEMM (with web_t_kernel_b3<true>, T is never stored):
-// gX1[p][a] += Σ_{k,b} gm[p][k] x2[p][b] W[a][b][k]; A = gm·x2 scaled while staging,
-// B = Wg[k][a][b]; 32-deep chunks of b for each k ----
-__global__ void __launch_bounds__(256) web_gx1_kernel_b3(const float *__restrict__ X2,
-                                                         const float *__restrict__ GM,
-                                                         const float *__restrict__ Wg,
-                                                         const int2 *__restrict__ ext128,
-                                                         int64_t n, int Dp, int K,
-                                                         float *__restrict__ GX1) {
-  __shared__ __attribute__((aligned(16))) uint16_t sA[3 * B3PART], sB[3 * B3PART];
-  int pb, at, kk_;
-  web_pb_tile(Dp / TB, (int)((n + TB * 8 - 1) / (TB * 8)), pb, at, kk_);
-  if ((int64_t)pb * TB >= n) return;
-  const int64_t p0 = (int64_t)pb * TB;
-  const int a0 = at * TB;
-  const int2 e = ext128[pb];
-  if (a0 >= e.x) return;
-  const int nb = (e.y + B3K - 1) / B3K * B3K;
-  const int tid = threadIdx.x, l = tid & 63, w = tid >> 6, i = l & 15, g = l >> 4;
-  const int wm = w >> 1, wn = w & 1;
-  float4 ra[4], rb[4];
-  float gmr[4];
-  auto load = [&](int k, int b0, bool xload) {
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int q = tid + 256 * u, r = q >> 3, c = (q & 7) * 4;
-      const int64_t p = p0 + r;
-      gmr[u] = p < n ? GM[p * WKP + k] : 0.f;
-      if (xload) ra[u] = *(const float4 *)(X2 + p * Dp + b0 + c);
-      rb[u] = *(const float4 *)(Wg + ((size_t)k * Dp + a0 + r) * Dp + b0 + c);
-    }
-  };
-  f4 acc[4][4];
-#pragma unroll
-  for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-    for (int ni = 0; ni < 4; ++ni) acc[mi][ni] = f4{0.f, 0.f, 0.f, 0.f};
-  const int steps = nb / B3K, total = K * steps;
-  if (total > 0) load(0, 0, true);
-  for (int st = 0; st < total; ++st) {
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int q = tid + 256 * u, r = q >> 3, c = (q & 7) * 4;
-      const float gm = gmr[u];
-      b3_split_store(sA, r, c, make_float4(gm * ra[u].x, gm * ra[u].y, gm * ra[u].z, gm * ra[u].w));
-      b3_split_store(sB, r, c, rb[u]);
-    }
-    __syncthreads();
-    if (st + 1 < total) {
-      const int s1 = st + 1;
-      load(s1 % K, (s1 / K) * B3K, s1 % K == 0);
-    }
-#pragma unroll
-    for (int mi = 0; mi < 4; ++mi) {
-      const int oa = (wm * 64 + mi * 16 + i) * B3S + 8 * g;
-      const uint4 ah = *(const uint4 *)(sA + oa), am = *(const uint4 *)(sA + B3PART + oa),
-                  al = *(const uint4 *)(sA + 2 * B3PART + oa);
-#pragma unroll
-      for (int ni = 0; ni < 4; ++ni) {
-        const int ob = (wn * 64 + ni * 16 + i) * B3S + 8 * g;
-        const uint4 bh = *(const uint4 *)(sB + ob), bm = *(const uint4 *)(sB + B3PART + ob),
-                    bl = *(const uint4 *)(sB + 2 * B3PART + ob);
-        f4 c = acc[mi][ni];
-        c = sgk::mfbf(al, bh, c);
-        c = sgk::mfbf(ah, bl, c);
-        c = sgk::mfbf(am, bm, c);
-        c = sgk::mfbf(am, bh, c);
-        c = sgk::mfbf(ah, bm, c);
-        c = sgk::mfbf(ah, bh, c);
-        acc[mi][ni] = c;
-      }
-    }
-    __syncthreads();
-  }
-#pragma unroll
-  for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int64_t p = p0 + wm * 64 + mi * 16 + 4 * g + r;
-      if (p >= n) continue;
-      float *dst = GX1 + p * Dp + a0 + wn * 64 + i;
+      float *dst = GXout + p * Dp + o0 + wn * 64 + i;
 #pragma unroll
       for (int ni = 0; ni < 4; ++ni) dst[ni * 16] += acc[mi][ni][r];
     }
@@ -1639,14 +1431,7 @@ __global__ void __launch_bounds__(256) web_wgrad_kernel_b3(const float *__restri
           const int ob = (wn * 64 + ni * 16 + i) * B3S + 8 * g;
           const uint4 bh = *(const uint4 *)(sB + ob), bm = *(const uint4 *)(sB + B3PART + ob),
                       bl = *(const uint4 *)(sB + 2 * B3PART + ob);
-          f4 c = acc[mi][ni];
-          c = sgk::mfbf(al, bh, c);
-          c = sgk::mfbf(ah, bl, c);
-          c = sgk::mfbf(am, bm, c);
-          c = sgk::mfbf(am, bh, c);
-          c = sgk::mfbf(ah, bm, c);
-          c = sgk::mfbf(ah, bh, c);
-          acc[mi][ni] = c;
+          b3_mma6(acc[mi][ni], ah, am, al, bh, bm, bl);
         }
       }
       __syncthreads();
@@ -1677,13 +1462,13 @@ __global__ void __launch_bounds__(256) web_wgrad_kernel_b3(const float *__restri
 }
 
 // ---------------------------------------------------------------------------
-// Per-pair NTN head: m_k, s, ŷ, loss, gm; gx1 = Σ_k gm_k (T_k + V_k),
-// gx2 := Σ_k gm_k V_k[D + ·] (web_gx2 adds the W term).  One wave per pair.
+// Per-pair NTN head: m_k, s, ŷ, loss, gm; gx1 := Σ_k gm_k V_k, gx2 := Σ_k gm_k V_k[D + ·]
+// (web_gx_kernel_b3 adds their W terms).  One wave per pair.
 // ---------------------------------------------------------------------------
 struct HeadArgs {
   const float *X, *T, *params, *labels, *y_stats;
   const int2 *ext;
-  const int2 *ext128;   // MT: per-128-pair extents (which a-tiles web_t_kernel_b3 computed)
+  const int2 *ext128;   // per-128-pair extents (which a-tiles the T kernel computed)
   float *GX, *GM, *s_out, *hslab;
   int64_t n, Cp;
   int D, Dp, K, oV, oU, obn;
@@ -1691,9 +1476,9 @@ struct HeadArgs {
   float yeta, inv_batch;
 };
 
-// MT: T holds web_t_kernel_b3<true>'s a-tile shares MP[p][k][tile] of Σ_a x1[a] T[k][a]
-// instead of T, and gx1 gets only its V term here (web_gx1_kernel_b3 adds the T term)
-template <bool BWD, bool MT>
+// T holds the T kernel's a-tile shares MP[p][k][tile] of Σ_a x1[a] T[k][a], and gx1 gets
+// only its V term here (web_gx_kernel_b3<false> adds the T term)
+template <bool BWD>
 __global__ void __launch_bounds__(256) web_head_kernel(HeadArgs A) {
   extern __shared__ __attribute__((aligned(16))) float sV[];   // [K][2Dp]: V[k][a] | V[k][D+b]
   const int tid = threadIdx.x, l = tid & 63, w = tid >> 6;
@@ -1718,13 +1503,11 @@ __global__ void __launch_bounds__(256) web_head_kernel(HeadArgs A) {
   const int64_t gw = (int64_t)blockIdx.x * 4 + w, nw = (int64_t)gridDim.x * 4;
   for (int64_t p = gw; p < A.n; p += nw) {
     const int2 ex = A.ext[p];
-    const int e1 = ex.x;
     // x1 / x2 are zero past the extents (padding 0) and gx past them is never read (the
     // instance kernels take ∂L/∂x of present nodes only): 64-wide column blocks up to the
     // larger extent
     const int ncp = min(nc, (max(ex.x, ex.y) + 63) >> 6);
     const float *x1 = A.X + p * Dp, *x2 = A.X + (A.Cp + p) * Dp;
-    const float *Tp = A.T + (size_t)p * K * Dp;
     float m[WKP];
 #pragma unroll
     for (int k = 0; k < WKP; ++k) m[k] = 0.f;
@@ -1734,16 +1517,15 @@ __global__ void __launch_bounds__(256) web_head_kernel(HeadArgs A) {
 #pragma unroll
       for (int k = 0; k < WKP; ++k) {
         if (k < K) {
-          const float t = (!MT && a < e1) ? Tp[k * Dp + a] : 0.f;
-          m[k] = fmaf(xa, t + sV[k * 2 * Dp + a], m[k]);
+          m[k] = fmaf(xa, 0.f + sV[k * 2 * Dp + a], m[k]);   // 0 + V: a -0 in V counts as +0
           m[k] = fmaf(xb, sV[k * 2 * Dp + Dp + a], m[k]);
         }
       }
     }
-    float mt[WKP];   // MT: the bilinear term from the a-tile shares, tiles in order
+    float mt[WKP];   // the bilinear term from the a-tile shares, tiles in order
 #pragma unroll
     for (int k = 0; k < WKP; ++k) mt[k] = 0.f;
-    if (MT) {
+    {
       const int ex = A.ext128[p / TB].x;
       const float *mp = A.T + (size_t)p * WKP * 4;
 #pragma unroll
@@ -1801,8 +1583,7 @@ __global__ void __launch_bounds__(256) web_head_kernel(HeadArgs A) {
 #pragma unroll
       for (int k = 0; k < WKP; ++k) {
         if (k < K) {
-          const float t = (!MT && a < e1) ? Tp[k * Dp + a] : 0.f;
-          v1 = fmaf(gm[k], t + sV[k * 2 * Dp + a], v1);
+          v1 = fmaf(gm[k], 0.f + sV[k * 2 * Dp + a], v1);   // as in m[k] above
           v2 = fmaf(gm[k], sV[k * 2 * Dp + Dp + a], v2);
         }
       }
@@ -1878,10 +1659,6 @@ __global__ void __launch_bounds__(256) web_vsum(const float *__restrict__ GVS, i
   gV[x] = v;
 }
 
-__global__ void web_copy_scalar(const float *__restrict__ src, float *__restrict__ dst) {
-  if (threadIdx.x == 0) dst[0] = src[0];
-}
-
 }  // namespace
 
 // ===========================================================================
@@ -1909,16 +1686,6 @@ int64_t sg_web_ws_bytes(const sg_model_t *m, int64_t chunk, int64_t n_pairs) {
   return (one ? ws.total1 : ws.total) * 4 + 256;
 }
 
-// A/B: dynamic LDS padding of a GEMM launch (bytes, from the environment), which lowers the
-// blocks a CU holds at once (the GEMMs hold ≈61-67 KB of static LDS: 2 blocks per CU)
-static size_t web_lds_pad(const char *name, const void *fn) {
-  const char *e = getenv(name);
-  const int v = e ? atoi(e) : 0;
-  if (v <= 0) return 0;
-  (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, v);
-  return (size_t)v;
-}
-
 static int web_status() {
   const hipError_t e = hipGetLastError();
   if (e == hipSuccess) return SG_OK;
@@ -1926,10 +1693,10 @@ static int web_status() {
   return SG_ERR_HIP;
 }
 
-// LDS of the instance kernel (+ the CSR rows with LCSR)
-static size_t gcn_lds_bytes(const WebPlan &W, int n_max, int max_nnz, bool bwd, bool lcsr) {
+// LDS of the instance kernel
+static size_t gcn_lds_bytes(const WebPlan &W, int n_max, bool bwd) {
   const int n16 = (n_max + 15) & ~15;
-  const GcnLds L = gcn_lds(W.d_in, n16, max_nnz, bwd, lcsr);
+  const GcnLds L = gcn_lds(W.d_in, n16, bwd);
   size_t lds = (size_t)L.total * 4u;
   if (bwd) {
     const size_t fl = ((size_t)L.tables + 8u * (size_t)W.n_gcn) * 4u;
@@ -1940,16 +1707,8 @@ static size_t gcn_lds_bytes(const WebPlan &W, int n_max, int max_nnz, bool bwd, 
 
 static int gcn_launch(bool bwd, const WebPlan &W, const GcnArgs &A, int64_t n_inst,
                       hipStream_t st) {
-  // CSR rows staged in LDS (LCSR) measured slower than reading them through the caches
-  // once the instance kernels run 16 waves (forward 14.7 -> 13.1 ms per chunk without),
-  // so it is opt-in (SG_WEB_LCSR=1); the backward's LDS no longer fits it at 16 waves
-  static const bool want_lcsr = getenv("SG_WEB_LCSR") != nullptr;
-  const bool lcsr = want_lcsr && gcn_lds_bytes(W, A.n_max, A.max_nnz, bwd, true) <= 163840u &&
-                    A.max_nnz <= 4096;
-  const size_t lds = gcn_lds_bytes(W, A.n_max, A.max_nnz, bwd, lcsr);
+  const size_t lds = gcn_lds_bytes(W, A.n_max, bwd);
   if (lds > 163840u) return SG_ERR_UNSUPPORTED;
-  GcnArgs A_ = A;
-  if (lcsr) A_.isorted = nullptr, A_.icls = nullptr;   // LCSR stages one instance at a time
   int per_cu = (int)(163840u / lds);
   if (per_cu > 2048 / (64 * gcn_gw(bwd))) per_cu = 2048 / (64 * gcn_gw(bwd));
   if (!bwd) {
@@ -1965,38 +1724,24 @@ static int gcn_launch(bool bwd, const WebPlan &W, const GcnArgs &A, int64_t n_in
   if (bwd) blocks = sg_num_cus();   // one slab row per block (web_ws sizes the slab for this)
   if (blocks > n_inst) blocks = n_inst;
   if (blocks < 1) return SG_OK;
-#define SG_WEB_GCN(B, NT, LC)                                                                   \
-  do {                                                                                        \
-    const void *fn = (const void *)web_gcn_kernel<B, NT, LC>;                                 \
-    (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);      \
-    hipLaunchKernelGGL((web_gcn_kernel<B, NT, LC>), dim3((unsigned)blocks), dim3(64 * gcn_gw(B)), \
-                       lds, st, A_);                                                          \
-  } while (0)
-#define SG_WEB_GCN_NT(NT)                             \
-  do {                                                \
-    if (bwd) {                                        \
-      if (lcsr) SG_WEB_GCN(true, NT, true);           \
-      else SG_WEB_GCN(true, NT, false);               \
-    } else {                                          \
-      if (lcsr) SG_WEB_GCN(false, NT, true);          \
-      else SG_WEB_GCN(false, NT, false);              \
-    }                                                 \
-  } while (0)
+  void (*fn)(GcnArgs);
+#define SG_WEB_GCN(NT) fn = bwd ? web_gcn_kernel<true, NT> : web_gcn_kernel<false, NT>
   switch (W.tb) {
-    case 1: SG_WEB_GCN_NT(1); break;
-    case 2: SG_WEB_GCN_NT(2); break;
-    case 3: SG_WEB_GCN_NT(3); break;
-    default: SG_WEB_GCN_NT(4); break;
+    case 1: SG_WEB_GCN(1); break;
+    case 2: SG_WEB_GCN(2); break;
+    case 3: SG_WEB_GCN(3); break;
+    default: SG_WEB_GCN(4); break;
   }
-#undef SG_WEB_GCN_NT
 #undef SG_WEB_GCN
+  (void)hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  hipLaunchKernelGGL(fn, dim3((unsigned)blocks), dim3(64 * gcn_gw(bwd)), lds, st, A);
   return SG_OK;
 }
 
 int sg_web_lds_ok(const sg_model_t *m) {
   WebPlan W;
   if (web_plan(m, &W) != SG_OK) return 0;
-  return gcn_lds_bytes(W, m->n_max, 0, true, false) <= 163840u;
+  return gcn_lds_bytes(W, m->n_max, true) <= 163840u;
 }
 
 // The chunk pipeline's second stream and its events (sg_web_run: F = a chunk's forward
@@ -2260,8 +2005,7 @@ int sg_web_run(const sg_model_t *m, const sg_csr_store_t *store, const int32_t *
       hipLaunchKernelGGL(web_t_kernel_kg, dim3((unsigned)nblk, Dp / TB, (K + TKG - 1) / TKG),
                          dim3(512), 0, gs, X + ws.Cp * Dp, Wg, S.EXT128, n, Dp, K, T, X);
     else
-      hipLaunchKernelGGL(web_t_kernel_b3<true>, web_pb_grid(nblk, Dp / TB, K), dim3(256),
-                         web_lds_pad("SG_WEB_TPAD", (const void *)web_t_kernel_b3<true>), gs,
+      hipLaunchKernelGGL(web_t_kernel_b3, dim3((unsigned)nblk, Dp / TB, K), dim3(256), 0, gs,
                          X + ws.Cp * Dp, Wg, S.EXT128, n, Dp, K, T, X);
     HeadArgs h = H;
     h.X = X; h.T = T; h.ext = S.EXT; h.ext128 = S.EXT128; h.GX = GX; h.GM = GM;
@@ -2270,19 +2014,17 @@ int sg_web_run(const sg_model_t *m, const sg_csr_store_t *store, const int32_t *
     h.s_out = s_out ? s_out + c0 : nullptr;
     const int hb = (int)((n + 3) / 4 < ws.head_blocks ? (n + 3) / 4 : ws.head_blocks);
     if (bwd) {
-      hipLaunchKernelGGL((web_head_kernel<true, true>), dim3(hb), dim3(256), head_lds, gs, h);
-      hipLaunchKernelGGL(web_gx1_kernel_b3, web_pb_grid(nblk, Dp / TB, 1), dim3(256),
-                         web_lds_pad("SG_WEB_GXPAD", (const void *)web_gx1_kernel_b3), gs,
-                         X + ws.Cp * Dp, GM, Wg, S.EXT128, n, Dp, K, GX);
-      hipLaunchKernelGGL(web_gx2_kernel_b3, web_pb_grid(nblk, Dp / TB, 1), dim3(256),
-                         web_lds_pad("SG_WEB_GXPAD", (const void *)web_gx2_kernel_b3), gs, X,
-                         GM, Wh, S.EXT128, n, Dp, K, GX + ws.Cp * Dp);
+      hipLaunchKernelGGL(web_head_kernel<true>, dim3(hb), dim3(256), head_lds, gs, h);
+      const dim3 gxg((unsigned)nblk, Dp / TB, 1);
+      hipLaunchKernelGGL(web_gx_kernel_b3<false>, gxg, dim3(256), 0, gs, X + ws.Cp * Dp, GM, Wg,
+                         S.EXT128, n, Dp, K, GX);
+      hipLaunchKernelGGL(web_gx_kernel_b3<true>, gxg, dim3(256), 0, gs, X, GM, Wh, S.EXT128, n,
+                         Dp, K, GX + ws.Cp * Dp);
       // gV rides along
       hipLaunchKernelGGL(web_wgrad_kernel_b3, dim3((Dp / TB) * (Dp / TB), K, WSPLIT), dim3(256),
-                         web_lds_pad("SG_WEB_WGPAD", (const void *)web_wgrad_kernel_b3), gs, X,
-                         X + ws.Cp * Dp, GM, S.EXT16, n, Dp, K, GWS, GVS);
+                         0, gs, X, X + ws.Cp * Dp, GM, S.EXT16, n, Dp, K, GWS, GVS);
     } else {
-      hipLaunchKernelGGL((web_head_kernel<false, true>), dim3(hb), dim3(256), head_lds, gs, h);
+      hipLaunchKernelGGL(web_head_kernel<false>, dim3(hb), dim3(256), head_lds, gs, h);
     }
   };
   // chunk c's backward instance kernel (stream st)
