@@ -205,6 +205,12 @@ def lib():
     L.sg_embed_bwd_workspace_bytes.restype = c_i64
     L.sg_embed_bwd.argtypes = [pm, vp, vp, vp, c_i32, c_i32, vp, c_i64, vp, vp, vp, vp, vp, vp]
     L.sg_embed_bwd.restype = c_i32
+    # embed-once search (include/siamese_search.h)
+    L.sg_search_topk_workspace_bytes.argtypes = [pm, c_i64, c_i64, c_i32, c_i64]
+    L.sg_search_topk_workspace_bytes.restype = c_i64
+    L.sg_search_topk.argtypes = [pm, vp, vp, c_i64, c_i64, vp, c_i32, c_i32, c_i32, c_i64, vp,
+                                 vp, vp, vp]
+    L.sg_search_topk.restype = c_i32
     _lib = L
     return L
 
@@ -233,6 +239,10 @@ EMBED_SYMBOLS = ('sg_embed_dim', 'sg_embed', 'sg_score_grid_workspace_bytes', 's
 # caller detects the feature, sg_version() does not change with them)
 EMBED_TRAIN_SYMBOLS = ('sg_score_grid_bwd_workspace_bytes', 'sg_score_grid_fwd_bwd',
                        'sg_embed_bwd_workspace_bytes', 'sg_embed_bwd')
+
+# the symbols of include/siamese_search.h (embed-once search: score grid + top-k in one call,
+# no m x n matrix; detected by presence, like the training symbols)
+SEARCH_SYMBOLS = ('sg_search_topk_workspace_bytes', 'sg_search_topk')
 
 # class_start entries of sg_pair_order_cls (include/siamese_hip.h SG_FAST_CLASSES_P1)
 FAST_CLASSES_P1 = 5
@@ -563,6 +573,25 @@ def embed_bwd(m: SgModel, store_dev, n_max, graph_idx, count, params, g_emb, gra
 def topk_rows(vals, m, n, ld, k, largest, idx_out, val_out=None, stream=None):
     check(lib().sg_topk_rows(_ptr(vals), int(m), int(n), int(ld), int(k), int(bool(largest)),
                              _ptr(idx_out), _ptr(val_out), _stream(stream)), 'sg_topk_rows')
+
+
+def search_workspace_bytes(m: SgModel, n_q: int, n_db: int, k: int, seg_cols: int = 0) -> int:
+    b = int(lib().sg_search_topk_workspace_bytes(ctypes.byref(m), int(n_q), int(n_db), int(k),
+                                                 int(seg_cols)))
+    if b < 0:
+        raise SiameseHipError('sg_search_topk_workspace_bytes: the search serves the NTN head '
+                              'with input_dim <= 31 and feature_map_dim <= 16, 1 <= k <= '
+                              'min(n, 64) and seg_cols = 0 or a positive multiple of 64')
+    return b
+
+
+def search_topk(m: SgModel, emb_q, emb_db, n_q, n_db, params, apply_final, k, largest, seg_cols,
+                idx_out, val_out, workspace, stream=None):
+    """sg_search_topk: what score_grid + topk_rows return, without the [n_q][n_db] matrix."""
+    check(lib().sg_search_topk(ctypes.byref(m), _ptr(emb_q), _ptr(emb_db), int(n_q), int(n_db),
+                               _ptr(params), int(bool(apply_final)), int(k), int(bool(largest)),
+                               int(seg_cols), _ptr(idx_out), _ptr(val_out), _ptr(workspace),
+                               _stream(stream)), 'sg_search_topk')
 
 
 def seed_advance(seed_dev, delta=1, stream=None):

@@ -123,18 +123,8 @@ __global__ void __launch_bounds__(256) sg_grid_kernel(GridArgs A) {
 // Top-k of each row: one wavefront per row, k selection rounds.  Every element maps to a
 // 64-bit key (rank of the value, column) whose unsigned order is the documented total
 // order; a round scans the row for the smallest key strictly above the previous round's,
-// then reduces over the wavefront.  The input is only read.
+// then reduces over the wavefront (topk_key: sg_embed_plan.h).  The input is only read.
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ uint64_t topk_key(float x, uint32_t col, int largest) {
-  uint32_t rk = 0xFFFFFFFFu;   // NaN: after every number
-  if (x == x) {
-    const uint32_t u = x == 0.f ? 0u : __float_as_uint(x);   // -0 ranks with +0
-    const uint32_t asc = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-    rk = largest ? ~asc : asc;   // both within [0x007FFFFF, 0xFF800000]
-  }
-  return ((uint64_t)rk << 32) | col;
-}
-
 __global__ void __launch_bounds__(256) sg_topk_kernel(const float *__restrict__ vals, int64_t m,
                                                       int64_t n, int64_t ld, int k, int largest,
                                                       int32_t *__restrict__ idx,

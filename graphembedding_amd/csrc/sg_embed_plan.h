@@ -1,10 +1,11 @@
 // sg_embed_plan.h — what the embed-once translation units share (sg_embed.hip: retrieval,
-// include/siamese_embed.h; sg_embed_train.hip: training, include/siamese_embed_train.h):
+// include/siamese_embed.h; sg_embed_train.hip: training, include/siamese_embed_train.h;
+// sg_search.hip: search, include/siamese_search.h):
 // the dropout-off plan of a model; the store side of the two embedding kernels (which
-// graphs a wavefront takes, what it reports, Â and the types staged in its LDS slice); and
+// graphs a wavefront takes, what it reports, Â and the types staged in its LDS slice);
 // the NTN score grid's limits, query-chunk split, common kernel arguments, per-query table
-// kernel and MFMA operand helpers.  Internal linkage throughout: each unit compiles its
-// own copy.
+// kernel and MFMA operand helpers; and the key of the top-k selections' total order.
+// Internal linkage throughout: each unit compiles its own copy.
 #pragma once
 #include <type_traits>
 
@@ -272,6 +273,22 @@ __device__ __forceinline__ const float *grid_load_q(const GridCommon &A, int64_t
 #pragma unroll
   for (int s = 0; s < NS; ++s) b[s] = Qi[s * 64 + lane];
   return Qi;
+}
+
+// ---------------------------------------------------------------------------
+// The total order of the top-k selections (sg_topk_rows, sg_search_topk): a 64-bit key
+// (rank of the value, column) whose unsigned order is by value (descending when largest),
+// ties to the smaller column, NaN after every number and by column.  Keys of distinct
+// columns differ, and every key is below ~0 (columns are < 2^31).
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ uint64_t topk_key(float x, uint32_t col, int largest) {
+  uint32_t rk = 0xFFFFFFFFu;   // NaN: after every number
+  if (x == x) {
+    const uint32_t u = x == 0.f ? 0u : __float_as_uint(x);   // -0 ranks with +0
+    const uint32_t asc = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+    rk = largest ? ~asc : asc;   // both within [0x007FFFFF, 0xFF800000]
+  }
+  return ((uint64_t)rk << 32) | col;
 }
 
 }  // namespace

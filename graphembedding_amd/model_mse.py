@@ -589,6 +589,30 @@ class SiameseGCNTNMSE(object):
         _lib.topk_rows(s, m, n, n, k, largest, idx, val)
         return idx, val
 
+    def search(self, emb_q, emb_db, k, largest=True, final=True, seg_cols=0):
+        """(idx int32 [m][k], values [m][k]): topk(score_grid(emb_q, emb_db, final), k,
+        largest), bit for bit, from one fused call that never holds the [m][n] scores
+        (include/siamese_search.h).  seg_cols: database columns per workgroup, 0 = the
+        library's choice; the result does not depend on it."""
+        torch = self.torch
+        self._no_web('search')
+        d = self.embed_dim
+        q = torch.as_tensor(emb_q, dtype=torch.float32, device=self.device).contiguous()
+        db = torch.as_tensor(emb_db, dtype=torch.float32, device=self.device).contiguous()
+        if q.dim() != 2 or db.dim() != 2 or q.shape[1] != d or db.shape[1] != d:
+            raise _lib.SiameseHipError('search: embeddings must be [*, {}]'.format(d))
+        m, n = int(q.shape[0]), int(db.shape[0])
+        nbytes = _lib.search_workspace_bytes(self.sg, m, n, k, seg_cols)
+        ws = getattr(self, '_search_ws', None)      # the last workspace, kept while it fits
+        if ws is None or ws.numel() * 4 < nbytes or ws.device != q.device:
+            ws = torch.empty(nbytes // 4 + 1, dtype=torch.float32, device=self.device)
+            self._search_ws = ws
+        idx = torch.empty((m, int(k)), dtype=torch.int32, device=self.device)
+        val = torch.empty((m, int(k)), dtype=torch.float32, device=self.device)
+        _lib.search_topk(self.sg, q, db, m, n, self.params, final, k, largest, seg_cols, idx,
+                         val, ws)
+        return idx, val
+
     # ---- embed-once training (include/siamese_embed_train.h; dropout 0 only) ----
     def _no_dropout(self, what):
         if self.flags.dropout != 0:

@@ -34,3 +34,9 @@ class EmbeddingIndex(object):
         """(idx int32 [m][k], sims [m][k]): the k most similar indexed graphs per query,
         best first, ties to the smaller index."""
         return self.model.topk(self.scores(query_graphs), k, largest=largest)
+
+    def search(self, query_graphs: Sequence, k: int, largest: bool = True):
+        """What topk returns, from one fused call that keeps a running top-k per query on
+        the chip and never holds the [m][n] similarity matrix (include/siamese_search.h):
+        the way to query an index too large for `scores`."""
+        return self.model.search(self._embed(query_graphs), self.embeddings, k, largest=largest)

@@ -12,6 +12,16 @@ Times, alternated `--repeats` times in one process (device events, warmed up):
       its 4 B per pair of output.
 Prints one JSON line; (a) and (b) compute the same matrix up to dropout (checked at
 dropout 0 within 1e-4 before timing).
+
+    python scripts/retrieval_bench.py --search [--repeats 3] [--out FILE.json]
+
+runs leg (d) alone, by the same protocol: the fused sg_search_topk against sg_score_grid +
+sg_topk_rows of the same build on synthetic embeddings,
+  (d1) 4096 x 4096, k = 10;
+  (d2) 256 x 1,048,576, k = 10 and k = 64 (the two-call way holds its 1 GB matrix),
+with both ways' workspace bytes.  The two ways must agree bit for bit before they are timed.
+"fused_wins": the fused median is below the two-call median by more than the larger
+max - min of the repeats.
 """
 import json
 import os
@@ -40,7 +50,85 @@ def timed(fn, iters):
     return a.elapsed_time(b) / iters
 
 
+def search_leg():
+    """Leg (d): sg_search_topk against sg_score_grid + sg_topk_rows."""
+    import torch
+    from graphembedding_amd import _lib
+    from graphembedding_amd.config import Flags
+    from graphembedding_amd.model_mse import SiameseGCNTNMSE
+    if not torch.cuda.is_available():
+        raise SystemExit('retrieval_bench needs a GPU (there is no CPU fallback)')
+    dev = torch.device('cuda', 0)
+    repeats = _arg('--repeats', 3)
+    model = SiameseGCNTNMSE(29, Flags(), device=dev, n_max=10)     # AIDS700nef's 29 types
+    E = model.embed_dim
+    rng = np.random.default_rng(0)
+    shapes = [('d1_4096x4096_k10', 4096, 4096, 10, 20), ('d2_256x1048576_k10', 256, 1 << 20, 10, 3),
+              ('d2_256x1048576_k64', 256, 1 << 20, 64, 1)]
+    emb = {}
+    for rows in (256, 4096, 1 << 20):
+        emb[rows] = torch.from_numpy(rng.uniform(0, 1, size=(rows, E)).astype(np.float32)).to(dev)
+    cases, info = [], {}
+    for name, m, n, k, iters in shapes:
+        q, db = emb[m], emb[n]
+        ws2_bytes = _lib.score_grid_workspace_bytes(model.sg, m)
+        ws1_bytes = _lib.search_workspace_bytes(model.sg, m, n, k, 0)
+        ws2 = torch.empty(ws2_bytes // 4 + 1, dtype=torch.float32, device=dev)
+        ws1 = torch.empty(ws1_bytes // 4 + 1, dtype=torch.float32, device=dev)
+        out = torch.empty((m, n), dtype=torch.float32, device=dev)
+        idx2 = torch.empty((m, k), dtype=torch.int32, device=dev)
+        val2 = torch.empty((m, k), dtype=torch.float32, device=dev)
+        idx1, val1 = torch.empty_like(idx2), torch.empty_like(val2)
+
+        def two_call(q=q, db=db, m=m, n=n, k=k, out=out, ws2=ws2, idx2=idx2, val2=val2):
+            _lib.score_grid(model.sg, q, db, m, n, model.params, True, out, n, ws2)
+            _lib.topk_rows(out, m, n, n, k, True, idx2, val2)
+
+        def grid_only(q=q, db=db, m=m, n=n, out=out, ws2=ws2):
+            _lib.score_grid(model.sg, q, db, m, n, model.params, True, out, n, ws2)
+
+        def fused(q=q, db=db, m=m, n=n, k=k, ws1=ws1, idx1=idx1, val1=val1):
+            _lib.search_topk(model.sg, q, db, m, n, model.params, True, k, True, 0, idx1, val1,
+                             ws1)
+
+        two_call()
+        fused()
+        torch.cuda.synchronize()
+        assert torch.equal(idx1, idx2) and torch.equal(val1.view(torch.int32),
+                                                       val2.view(torch.int32)), name
+        cases += [(name + '/fused', fused, iters), (name + '/two_call', two_call, iters),
+                  (name + '/grid_only', grid_only, iters)]
+        info[name] = dict(m=m, n=n, k=k, iters=iters, fused_workspace_bytes=ws1_bytes,
+                          two_call_workspace_bytes=ws2_bytes, two_call_matrix_bytes=m * n * 4)
+    for _, fn, _ in cases:       # warm-up of every shape
+        timed(fn, 1)
+    ms = {k: [] for k, _, _ in cases}
+    for _ in range(repeats):     # alternated
+        for k, fn, iters in cases:
+            ms[k].append(timed(fn, iters))
+    for name in info:
+        f, t = ms[name + '/fused'], ms[name + '/two_call']
+        spread = max(max(f) - min(f), max(t) - min(t))
+        info[name].update(
+            msec_fused=f, msec_two_call=t, msec_grid_only=ms[name + '/grid_only'],
+            median_fused=float(np.median(f)), median_two_call=float(np.median(t)),
+            median_grid_only=float(np.median(ms[name + '/grid_only'])),
+            larger_spread=spread, two_call_over_fused=float(np.median(t) / np.median(f)),
+            fused_wins=bool(np.median(t) - np.median(f) > spread))
+    res = dict(leg='search', embed_dim=E, repeats=repeats, bitwise_equal=True, cases=info,
+               device=torch.cuda.get_device_name(0))
+    line = json.dumps(res)
+    print(line)
+    out = _arg('--out', '')
+    if out:
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+        with open(out, 'w') as f:
+            f.write(line + '\n')
+
+
 def main():
+    if '--search' in sys.argv[1:]:
+        return search_leg()
     import torch
     from graphembedding_amd import _lib
     from graphembedding_amd.allpairs import load_graph_set
