@@ -205,6 +205,15 @@ def lib():
     L.sg_embed_bwd_workspace_bytes.restype = c_i64
     L.sg_embed_bwd.argtypes = [pm, vp, vp, vp, c_i32, c_i32, vp, c_i64, vp, vp, vp, vp, vp, vp]
     L.sg_embed_bwd.restype = c_i32
+    # embed-once training with graph-keyed dropout (include/siamese_embed_drop.h)
+    L.sg_embed_drop.argtypes = [pm, vp, vp, vp, c_i32, c_i32, vp, c_i64, c_i64, vp, c_u64, vp, vp,
+                                vp]
+    L.sg_embed_drop.restype = c_i32
+    L.sg_embed_drop_bwd_workspace_bytes.argtypes = [pm, c_i64]
+    L.sg_embed_drop_bwd_workspace_bytes.restype = c_i64
+    L.sg_embed_drop_bwd.argtypes = [pm, vp, vp, vp, c_i32, c_i32, vp, c_i64, c_i64, vp, c_u64, vp,
+                                    vp, vp, vp, vp]
+    L.sg_embed_drop_bwd.restype = c_i32
     # embed-once search (include/siamese_search.h)
     L.sg_search_topk_workspace_bytes.argtypes = [pm, c_i64, c_i64, c_i32, c_i64]
     L.sg_search_topk_workspace_bytes.restype = c_i64
@@ -239,6 +248,10 @@ EMBED_SYMBOLS = ('sg_embed_dim', 'sg_embed', 'sg_score_grid_workspace_bytes', 's
 # caller detects the feature, sg_version() does not change with them)
 EMBED_TRAIN_SYMBOLS = ('sg_score_grid_bwd_workspace_bytes', 'sg_score_grid_fwd_bwd',
                        'sg_embed_bwd_workspace_bytes', 'sg_embed_bwd')
+
+# the symbols of include/siamese_embed_drop.h (embed-once training with graph-keyed dropout
+# masks; detected by presence, like the training symbols)
+EMBED_DROP_SYMBOLS = ('sg_embed_drop', 'sg_embed_drop_bwd_workspace_bytes', 'sg_embed_drop_bwd')
 
 # the symbols of include/siamese_search.h (embed-once search: score grid + top-k in one call,
 # no m x n matrix; detected by presence, like the training symbols)
@@ -568,6 +581,40 @@ def embed_bwd(m: SgModel, store_dev, n_max, graph_idx, count, params, g_emb, gra
                              int(n_max), _ptr(graph_idx), int(count), _ptr(params), _ptr(g_emb),
                              _ptr(grad_out), _ptr(status), _ptr(workspace), _stream(stream)),
           'sg_embed_bwd')
+
+
+def embed_drop(m: SgModel, store_dev, n_max, graph_idx, count, entry_offset, params, seed,
+               emb_out, status=None, stream=None):
+    """sg_embed_drop: sg_embed with graph-keyed dropout masks (entry c is side
+    (entry_offset + c) & 1 of unit (entry_offset + c) >> 1 under `seed`); emb_out receives
+    the embeddings through the head's input mask."""
+    adj, types, n = store_dev
+    check(lib().sg_embed_drop(ctypes.byref(m), _ptr(adj), _ptr(types), _ptr(n), int(n.numel()),
+                              int(n_max), _ptr(graph_idx), int(count), int(entry_offset),
+                              _ptr(params), int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(emb_out),
+                              _ptr(status), _stream(stream)), 'sg_embed_drop')
+
+
+def embed_drop_bwd_workspace_bytes(m: SgModel, count: int) -> int:
+    b = int(lib().sg_embed_drop_bwd_workspace_bytes(ctypes.byref(m), int(count)))
+    if b < 0:
+        raise SiameseHipError('sg_embed_drop_bwd_workspace_bytes: embed-once training with '
+                              'graph-keyed dropout serves valid models off the graph-store '
+                              'path whose stack fits the LDS')
+    return b
+
+
+def embed_drop_bwd(m: SgModel, store_dev, n_max, graph_idx, count, entry_offset, params, seed,
+                   g_emb, grad_out, workspace, status=None, stream=None):
+    """sg_embed_drop_bwd: the node layers' range of grad_out from g_emb [count][E], the
+    gradients of the masked embeddings embed_drop returned for the same entries and seed."""
+    adj, types, n = store_dev
+    check(lib().sg_embed_drop_bwd(ctypes.byref(m), _ptr(adj), _ptr(types), _ptr(n),
+                                  int(n.numel()), int(n_max), _ptr(graph_idx), int(count),
+                                  int(entry_offset), _ptr(params),
+                                  int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(g_emb), _ptr(grad_out),
+                                  _ptr(status), _ptr(workspace), _stream(stream)),
+          'sg_embed_drop_bwd')
 
 
 def topk_rows(vals, m, n, ld, k, largest, idx_out, val_out=None, stream=None):

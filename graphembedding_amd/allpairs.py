@@ -135,13 +135,14 @@ class AllPairsShard(object):
 
 
 class AllPairsGrid(object):
-    """The all-pairs step embed-once (dropout 0 only): AllPairsShard's counterpart for
-    model.grid_fwd_bwd.  Holds the G x G label matrix and its y_stats on the device; a step
+    """The all-pairs step embed-once: AllPairsShard's counterpart for model.grid_fwd_bwd
+    (dropout=None: flags.dropout = 0 only; dropout='graph': one dropout mask set per graph
+    per step, model.grid_fwd_bwd).  Holds the G x G label matrix and its y_stats on the device; a step
     embeds the G graphs once, runs the NTN grid forward + backward and one node-stack
     backward per graph instead of G² pair bodies (include/siamese_embed_train.h).  Same
     loss and gradient as AllPairsShard's batch at dropout 0, up to fp32 summation order."""
 
-    def __init__(self, gs: GraphSet, labels: np.ndarray, device='cuda'):
+    def __init__(self, gs: GraphSet, labels: np.ndarray, device='cuda', dropout=None):
         import torch
         G = len(gs.graphs)
         lab = np.ascontiguousarray(np.asarray(labels, np.float32).reshape(G, G))
@@ -152,6 +153,7 @@ class AllPairsGrid(object):
         ybar = y.mean()
         self.y_stats = torch.tensor([ybar, 0.5 * ((y - ybar) ** 2).sum()], dtype=torch.float32,
                                     device=device)
+        self.dropout = dropout
         self._problem = None
         self._owner = None
 
@@ -159,7 +161,8 @@ class AllPairsGrid(object):
         """The model's GridProblem of this grid (built once per model)."""
         owner = self._owner() if self._owner is not None else None
         if owner is not model:
-            self._problem = model.grid_problem(self.store, self.labels, y_stats=self.y_stats)
+            self._problem = model.grid_problem(self.store, self.labels, y_stats=self.y_stats,
+                                               dropout=self.dropout)
             self._owner = weakref.ref(model)
         return self._problem
 

@@ -1,7 +1,8 @@
 // sg_embed_plan.h — what the embed-once translation units share (sg_embed.hip: retrieval,
 // include/siamese_embed.h; sg_embed_train.hip: training, include/siamese_embed_train.h;
-// sg_search.hip: search, include/siamese_search.h):
-// the dropout-off plan of a model; the store side of the two embedding kernels (which
+// sg_search.hip: search, include/siamese_search.h; sg_embed_drop.hip: training with
+// graph-keyed dropout, include/siamese_embed_drop.h):
+// the dropout-off plan of a model and the plan that keeps its dropout; the store side of the two embedding kernels (which
 // graphs a wavefront takes, what it reports, Â and the types staged in its LDS slice);
 // the NTN score grid's limits, query-chunk split, common kernel arguments, per-query table
 // kernel and MFMA operand helpers; and the key of the top-k selections' total order.
@@ -25,6 +26,18 @@ int embed_plan(const sg_model_t *model, SgGenPlan *P) {
   if (sg_web_plan_params(model, &wn) == SG_OK && sg_web_lds_ok(model)) return SG_ERR_UNSUPPORTED;
   sg_model_t m = *model;
   m.keep_prob = 1.f;   // every threshold 65536: sg_keep is always true
+  m.adj_dtype = SG_DTYPE_F32;
+  return sg_build_plan(&m, P);
+}
+
+// The plan of the model with its own dropout (keep_prob and the per-layer dropout flags, as
+// the pair paths build it) and the f32 store: graph-keyed masks (sg_embed_drop.hip)
+int embed_drop_plan(const sg_model_t *model, SgGenPlan *P) {
+  if (!model) return SG_ERR_ARG;
+  if (!(model->keep_prob > 0.f && model->keep_prob <= 1.f)) return SG_ERR_ARG;
+  int64_t wn = 0;
+  if (sg_web_plan_params(model, &wn) == SG_OK && sg_web_lds_ok(model)) return SG_ERR_UNSUPPORTED;
+  sg_model_t m = *model;
   m.adj_dtype = SG_DTYPE_F32;
   return sg_build_plan(&m, P);
 }

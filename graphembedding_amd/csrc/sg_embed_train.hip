@@ -16,7 +16,7 @@
 //   g_emb_q[i][a] = Σ_{b<D,k} W[a][b][k] gQ_i[b][k] + Σ_k V[k][a] gQ_i[D][k].
 // Dropout 0 only: the header states why, train_plan refuses everything else.
 #include "../../include/siamese_embed_train.h"
-#include "sg_embed_plan.h"
+#include "sg_embed_bwd.h"
 #include "sg_mfma.h"
 
 namespace {
@@ -37,9 +37,6 @@ int train_plan(const sg_model_t *model, SgGenPlan *P, bool grid) {
       if (model->layers[li].dropout) return SG_ERR_UNSUPPORTED;
   return SG_OK;
 }
-
-// flat offset of the head's first variable: the node layers' range is [0, head_offset)
-int head_offset(const SgGenPlan &P) { return P.head_kind == SG_NTN ? P.offW : P.n_params; }
 
 // ---------------------------------------------------------------------------
 // Launch geometry and workspace layout of the grid call (host; independent of the device,
@@ -283,16 +280,6 @@ __global__ void __launch_bounds__(256) sg_grid_bwd_kernel(TrainGridArgs A) {
         bred[3][threadIdx.x];
 }
 
-// dst[c] = Σ_r src[r][c], rows in order (deterministic)
-__global__ void __launch_bounds__(256) sg_sum_rows(const float *__restrict__ src, int64_t rows,
-                                                   int64_t cols, float *__restrict__ dst) {
-  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (t >= cols) return;
-  float acc = 0.f;
-  for (int64_t r = 0; r < rows; ++r) acc += src[r * cols + t];
-  dst[t] = acc;
-}
-
 // ---------------------------------------------------------------------------
 // Table adjoint.  tab: one partial row [nT] = {gW, gV, gbias} per chunk of queries; gq:
 // g_emb_q; head: the fixed-order sums into grad_out's head range and loss_out.
@@ -426,12 +413,6 @@ __global__ void __launch_bounds__(256) sg_embed_bwd_kernel(SgGenPlan P, EmbedBwd
   __syncthreads();
   float *dst = A.slab + (size_t)blockIdx.x * (size_t)A.hoff;
   for (int i = threadIdx.x; i < A.hoff; i += blockDim.x) dst[i] = G[i];
-}
-
-// the generic kernel's backward shape with the node layers' gradient as the accumulator and
-// one unit per two graphs; the workspace is one slab row per workgroup of this shape
-SgGenLaunch embed_bwd_launch(const SgGenPlan &P, int64_t count) {
-  return sg_gen_launch_shape(P, head_offset(P), (count + 1) / 2);
 }
 
 }  // namespace

@@ -135,6 +135,7 @@ class GridProblem:
     status: object                  # torch.int32 [1] device status of sg_embed / sg_embed_bwd
     ws_grid: object
     ws_embed: object
+    dropout: Optional[str] = None   # None: dropout 0 only; 'graph': one mask set per graph
 
     def check(self):
         """Raise if a kernel reported a bad graph id or node count (synchronises)."""
@@ -613,24 +614,47 @@ class SiameseGCNTNMSE(object):
                          val, ws)
         return idx, val
 
-    # ---- embed-once training (include/siamese_embed_train.h; dropout 0 only) ----
+    # ---- embed-once training (include/siamese_embed_train.h: dropout 0 only;
+    # include/siamese_embed_drop.h: dropout='graph', masks keyed per graph) ----
     def _no_dropout(self, what):
         if self.flags.dropout != 0:
             raise _lib.SiameseHipError(
                 '{}: embed-once training needs flags.dropout = 0 (it is {}): the reference '
                 'draws its dropout masks per pair, so with dropout on a graph\'s embedding '
-                'depends on its partner; use fwd_bwd / train_step'.format(what,
-                                                                          self.flags.dropout))
+                'depends on its partner; use fwd_bwd / train_step, or dropout=\'graph\' '
+                '(one mask set per graph per step)'.format(what, self.flags.dropout))
 
-    def grid_problem(self, store: GraphStore, labels, q_idx=None, db_idx=None, y_stats=None):
+    def _grid_dropout(self, dropout, what):
+        """None: today's embed-once training, which refuses flags.dropout != 0; 'graph':
+        masks keyed per graph (include/siamese_embed_drop.h)."""
+        if dropout is None:
+            self._no_dropout(what)
+        elif dropout != 'graph':
+            raise _lib.SiameseHipError('{}: dropout must be None or \'graph\', not {!r}'.format(
+                what, dropout))
+
+    def _sg_keep1(self):
+        """A copy of the model struct with keep_prob = 1 (built once): what the grid calls
+        take when the head's mask is already in the embeddings."""
+        m = getattr(self, '_sg_keep1_copy', None)
+        if m is None:
+            m = _lib.SgModel.from_buffer_copy(self.sg)
+            m.keep_prob = 1.0
+            self._sg_keep1_copy = m
+        return m
+
+    def grid_problem(self, store: GraphStore, labels, q_idx=None, db_idx=None, y_stats=None,
+                     dropout=None):
         """The device-resident state of an m x n block of pairs (query q_idx[i] as graph 1,
         database db_idx[j] as graph 2; None = every store graph) with labels [m][n]: the
         distinct graphs, where each query / database entry sits among them, the labels and
         their {ȳ, ½Σ(y−ȳ)²} (float64, as AllPairsShard), and every buffer a step needs.
-        Build once, step many times (grid_fwd_bwd / grid_train_step)."""
+        Build once, step many times (grid_fwd_bwd / grid_train_step).
+        dropout: None serves flags.dropout = 0 only; 'graph' trains with dropout masks keyed
+        per graph (grid_fwd_bwd) and is stored on the problem."""
         torch = self.torch
         self._no_web('grid_problem')
-        self._no_dropout('grid_problem')
+        self._grid_dropout(dropout, 'grid_problem')
         self._check_store_capacity(store)
         self.check_node_counts(store.n, 'grid_problem')
         G = len(store)
@@ -664,11 +688,14 @@ class SiameseGCNTNMSE(object):
             emb=torch.empty((U, E), **f32), g_emb=torch.empty((U, E), **f32),
             g_q=torch.empty((m, E), **f32), g_db=torch.empty((n, E), **f32),
             status=torch.zeros(1, dtype=torch.int32, device=dev),
-            ws_grid=ws(_lib.score_grid_bwd_workspace_bytes(self.sg, m, n)),
-            ws_embed=ws(_lib.embed_bwd_workspace_bytes(self.sg, U)))
+            ws_grid=ws(_lib.score_grid_bwd_workspace_bytes(
+                self._sg_keep1() if dropout else self.sg, m, n)),
+            ws_embed=ws(_lib.embed_drop_bwd_workspace_bytes(self.sg, U) if dropout else
+                        _lib.embed_bwd_workspace_bytes(self.sg, U)),
+            dropout=dropout)
 
     def grid_fwd_bwd(self, store, labels=None, q_idx=None, db_idx=None, add_label_term=True,
-                     s_out=None):
+                     s_out=None, dropout=None, seed=None):
         """fwd_bwd over the m x n block of pairs, embed-once: every distinct graph's node
         stack runs forward once (sg_embed), the NTN grid runs forward and backward
         (sg_score_grid_fwd_bwd: loss, the head's gradient, the embeddings' gradients), the
@@ -677,13 +704,37 @@ class SiameseGCNTNMSE(object):
         self.loss_buf[0] exactly where fwd_bwd over the m·n pairs (batch_total = m·n) leaves
         them, up to fp32 summation order.  store: a GraphStore with labels [m][n], or a
         grid_problem(...) built once.  s_out: [m][n] pre-activation scores, optional.
-        Needs flags.dropout = 0 and the NTN head the score grid serves."""
-        self._no_dropout('grid_fwd_bwd')
-        gp = store if isinstance(store, GridProblem) else \
-            self.grid_problem(store, labels, q_idx, db_idx)
+        Needs the NTN head the score grid serves and, with dropout=None, flags.dropout = 0.
+
+        dropout='graph' (given here, or stored on the grid_problem) trains with dropout,
+        the masks keyed per graph: distinct graph c of the step (ascending store id) is
+        embedded as side c & 1 of unit c >> 1 under the step's seed (seed, default the
+        train steps' seed of step_count), with the node layers' masks and the NTN input mask
+        the generic pair kernel draws for that pair and side (sg_embed_drop); the grid runs
+        on the masked embeddings with keep_prob 1, and sg_embed_drop_bwd takes the summed
+        role gradients back under the same masks.  A graph that is both a query and a
+        database entry has ONE mask set per step, in both roles and in every pair.  This is
+        ordinary dropout of a batched Siamese model and deviates from the reference, which
+        draws fresh masks for every pair (quirk A4): the loss and gradient are not those of
+        fwd_bwd over the m·n pairs.  At flags.dropout = 0 it equals dropout=None."""
+        if isinstance(store, GridProblem):
+            gp = store
+            if dropout is not None and dropout != gp.dropout:
+                raise _lib.SiameseHipError('grid_fwd_bwd: dropout={!r} on a grid_problem built '
+                                           'with dropout={!r}'.format(dropout, gp.dropout))
+            self._grid_dropout(gp.dropout, 'grid_fwd_bwd')
+        else:
+            self._grid_dropout(dropout, 'grid_fwd_bwd')
+            gp = self.grid_problem(store, labels, q_idx, db_idx, dropout=dropout)
         sg, nmax = self.sg, self.n_max
         U = int(gp.uniq.numel())
-        _lib.embed(sg, gp.store_dev, nmax, gp.uniq, U, self.params, gp.emb, gp.status)
+        if gp.dropout:
+            seed = self._seed(seed)
+            sg = self._sg_keep1()   # the grid's model: the masks are in the embeddings
+            _lib.embed_drop(self.sg, gp.store_dev, nmax, gp.uniq, U, 0, self.params, seed,
+                            gp.emb, gp.status)
+        else:
+            _lib.embed(sg, gp.store_dev, nmax, gp.uniq, U, self.params, gp.emb, gp.status)
         eq, edb = (gp.emb, gp.emb) if gp.identity else (gp.emb[gp.q_pos], gp.emb[gp.db_pos])
         _lib.score_grid_fwd_bwd(sg, eq, edb, gp.m, gp.n, self.params, gp.labels, gp.n,
                                 gp.m * gp.n, gp.y_stats, add_label_term, s_out, gp.n, gp.g_q,
@@ -694,14 +745,20 @@ class SiameseGCNTNMSE(object):
             gp.g_emb.zero_()
             gp.g_emb.index_add_(0, gp.q_pos, gp.g_q)
             gp.g_emb.index_add_(0, gp.db_pos, gp.g_db)
-        _lib.embed_bwd(sg, gp.store_dev, nmax, gp.uniq, U, self.params, gp.g_emb, self.grad,
-                       gp.ws_embed, gp.status)
+        if gp.dropout:
+            _lib.embed_drop_bwd(self.sg, gp.store_dev, nmax, gp.uniq, U, 0, self.params, seed,
+                                gp.g_emb, self.grad, gp.ws_embed, gp.status)
+        else:
+            _lib.embed_bwd(sg, gp.store_dev, nmax, gp.uniq, U, self.params, gp.g_emb,
+                           self.grad, gp.ws_embed, gp.status)
         return gp
 
-    def grid_train_step(self, store, labels=None, q_idx=None, db_idx=None, sync=True):
+    def grid_train_step(self, store, labels=None, q_idx=None, db_idx=None, sync=True,
+                        dropout=None):
         """grid_fwd_bwd followed by Adam: train_step's embed-once counterpart (same loss
-        return: loss_mse + weight decay at the pre-update parameters)."""
-        self.grid_fwd_bwd(store, labels, q_idx, db_idx)
+        return: loss_mse + weight decay at the pre-update parameters).  With dropout='graph'
+        every step draws new masks (the seed follows step_count)."""
+        self.grid_fwd_bwd(store, labels, q_idx, db_idx, dropout=dropout)
         if self.grad_hook is not None:
             self.grad_hook(self)
         self.apply_adam()

@@ -1,6 +1,7 @@
 """Embed-once training against the pairwise step on the AIDS700nef-shaped set (GPU only).
 
     python scripts/grid_train_bench.py [--repeats 5] [--iters 20] [--out FILE.json]
+    python scripts/grid_train_bench.py --dropout [--repeats 5] [--iters 20] [--out FILE.json]
 
 One full all-pairs training step (forward, backward, Adam) of syn_aids700nef at dropout 0,
 timed `--repeats` times alternated in one process (device events, warmed up):
@@ -15,6 +16,13 @@ timed `--repeats` times alternated in one process (device events, warmed up):
 every variable's gradient within 1e-4 of its largest component).  The condition on (a) is
 median(a) < median(b) - spread, spread = the larger max - min of the two over the repeats;
 the ratio is reported, not asserted.  Prints one JSON line.
+
+--dropout measures what graph-keyed dropout (include/siamese_embed_drop.h) costs instead:
+the same step alternated between (d0) AllPairsGrid at dropout 0, as above, (dg) AllPairsGrid
+with dropout='graph' at dropout 0.1 and (dp) the pairwise fused step over the 490,000
+records at dropout 0.1, with the embed forward and backward of (d0) and (dg) alone.  The
+three compute different objectives (no masks, one mask set per graph, one per pair); only
+their times are compared.  No threshold: the medians and spreads are reported.
 """
 import json
 import os
@@ -41,6 +49,73 @@ def timed(fn, iters):
     b.record()
     torch.cuda.synchronize()
     return a.elapsed_time(b) / iters
+
+
+def dropout_main():
+    import torch
+    from graphembedding_amd import _lib
+    from graphembedding_amd.allpairs import AllPairsGrid, AllPairsShard, load_graph_set
+    from graphembedding_amd.config import Flags
+    from graphembedding_amd.model_mse import SiameseGCNTNMSE
+    if not torch.cuda.is_available():
+        raise SystemExit('grid_train_bench needs a GPU (there is no CPU fallback)')
+    dev = torch.device('cuda', 0)
+    repeats, iters = _arg('--repeats', 5), _arg('--iters', 20)
+    f0, f1 = Flags(dropout=0.0), Flags(dropout=0.1)
+    gs = load_graph_set('syn_aids700nef', n_max=10)
+    G = len(gs.mgs)
+    labels = gs.label_matrix(f0.yeta)
+    m0 = SiameseGCNTNMSE(gs.d_in, f0, device=dev, n_max=gs.n_max)
+    mg = SiameseGCNTNMSE(gs.d_in, f1, device=dev, n_max=gs.n_max, params=m0.flat_params())
+    mp = SiameseGCNTNMSE(gs.d_in, f1, device=dev, n_max=gs.n_max, params=m0.flat_params())
+    grid0, gridg = AllPairsGrid(gs, labels, dev), AllPairsGrid(gs, labels, dev, dropout='graph')
+    gp0, gpg = grid0.problem(m0), gridg.problem(mg)
+    batch = AllPairsShard(gs, labels, device=dev).batch(mp)   # class-ordered (balance)
+    assert mp.kernel_path == 1 and batch.cls is not None and mg.sg.keep_prob < 1.0
+    U, nmax = int(gp0.uniq.numel()), m0.n_max
+
+    def d0_embed():
+        _lib.embed(m0.sg, gp0.store_dev, nmax, gp0.uniq, U, m0.params, gp0.emb, gp0.status)
+
+    def dg_embed():
+        _lib.embed_drop(mg.sg, gpg.store_dev, nmax, gpg.uniq, U, 0, mg.params, 1, gpg.emb,
+                        gpg.status)
+
+    def d0_embed_bwd():
+        _lib.embed_bwd(m0.sg, gp0.store_dev, nmax, gp0.uniq, U, m0.params, gp0.g_emb, m0.grad,
+                       gp0.ws_embed, gp0.status)
+
+    def dg_embed_bwd():
+        _lib.embed_drop_bwd(mg.sg, gpg.store_dev, nmax, gpg.uniq, U, 0, mg.params, 1, gpg.g_emb,
+                            mg.grad, gpg.ws_embed, gpg.status)
+
+    cases = [('grid_step_d0', lambda: grid0.train_step(m0, sync=False)),
+             ('grid_step_graph_d01', lambda: gridg.train_step(mg, sync=False)),
+             ('pairwise_step_d01', lambda: mp.train_step(batch, sync=False)),
+             ('embed_d0', d0_embed), ('embed_drop_d01', dg_embed),
+             ('embed_bwd_d0', d0_embed_bwd), ('embed_drop_bwd_d01', dg_embed_bwd)]
+    for _, fn in cases:          # warm-up of every shape
+        timed(fn, 3)
+    ms = {k: [] for k, _ in cases}
+    for _ in range(repeats):     # alternated
+        for k, fn in cases:
+            ms[k].append(timed(fn, iters))
+    torch.cuda.synchronize()
+    gp0.check()
+    gpg.check()
+    med = {k: float(np.median(v)) for k, v in ms.items()}
+    res = dict(graphs=G, pairs=G * G, repeats=repeats, iters=iters, msec=ms, msec_median=med,
+               spread_msec={k: max(v) - min(v) for k, v in ms.items()},
+               graph_dropout_over_dropout0=med['grid_step_graph_d01'] / med['grid_step_d0'],
+               pairwise_over_graph_dropout=med['pairwise_step_d01'] / med['grid_step_graph_d01'],
+               device=torch.cuda.get_device_name(0), one_box=True)
+    line = json.dumps(res)
+    print(line)
+    out = _arg('--out', '')
+    if out:
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+        with open(out, 'w') as f:
+            f.write(line + '\n')
 
 
 def main():
@@ -162,4 +237,4 @@ def main():
 
 
 if __name__ == '__main__':
-    main()
+    dropout_main() if '--dropout' in sys.argv[1:] else main()
