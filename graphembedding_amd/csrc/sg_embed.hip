@@ -1,5 +1,5 @@
-// sg_embed.hip — embed-once retrieval (include/siamese_embed.h): graph-level embeddings
-// from the generic node stack, the NTN score grid as a batched small-k GEMM on
+// sg_embed.hip — embed-once retrieval (include/siamese_embed.h): the NTN score grid over
+// graph-level embeddings (sg_embed: sg_embed_nodes.hip) as a batched small-k GEMM on
 // v_mfma_f32_16x16x4_f32, and per-row top-k selection.
 //
 // The NTN head (layers.py:282-310) of (query i as graph 1, database j as graph 2) is
@@ -16,47 +16,6 @@ namespace {
 using sgk::f4;
 
 constexpr int kTopkMax = 64;
-
-// ---------------------------------------------------------------------------
-// Embeddings: one wavefront runs gen_forward_nodes on the two graphs stage_graph_pair
-// resolves and stages (sg_embed_plan.h).  The row of an entry that cannot be embedded is
-// zeroed; the missing partner of an odd tail has no row.
-// ---------------------------------------------------------------------------
-struct EmbedArgs : StoreArgs {
-  const float *params;
-  float *out;
-};
-
-__global__ void __launch_bounds__(256) sg_embed_kernel(SgGenPlan P, EmbedArgs A) {
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
-  float *S = smem + wave * P.wave_floats;
-  const SgGenLayer &last = P.L[P.nl - 1];
-  const int E = last.Rout * last.dout;
-  const int64_t npair = (A.count + 1) >> 1;
-  for (int64_t q = (int64_t)blockIdx.x * nw + wave; q < npair; q += (int64_t)gridDim.x * nw) {
-    int g[2], n[2];
-    bool ok[2], have[2];
-    float *adj;
-    int *types;
-    const bool run = stage_graph_pair(P, A, S, q, lane, g, n, ok, have, adj, types);
-    float *o0 = A.out + (size_t)(2 * q) * E, *o1 = o0 + E;
-    if (!run) {
-      for (int e = lane; e < E; e += SG_WAVE) {
-        o0[e] = 0.f;
-        if (have[1]) o1[e] = 0.f;
-      }
-      continue;
-    }
-    gen_forward_nodes(P, S, A.params, adj, types, n[0], n[1], 0u, lane);
-    const float *e0 = S + last.l_out;
-    for (int e = lane; e < E; e += SG_WAVE) {
-      o0[e] = ok[0] ? e0[e] : 0.f;
-      if (have[1]) o1[e] = ok[1] ? e0[E + e] : 0.f;
-    }
-    sg_wsync();   // the next graphs overwrite the slice
-  }
-}
 
 // ---------------------------------------------------------------------------
 // Score grid over the tables Q [m][Dp][16].  A workgroup owns 64 database rows (four
@@ -157,36 +116,6 @@ __global__ void __launch_bounds__(256) sg_topk_kernel(const float *__restrict__ 
 }  // namespace
 
 extern "C" {
-
-int32_t sg_embed_dim(const sg_model_t *model) {
-  SgGenPlan P;
-  if (embed_plan(model, &P) != SG_OK) return -1;
-  return plan_embed_dim(P);
-}
-
-int32_t sg_embed(const sg_model_t *model, const float *store_adj, const int32_t *store_types,
-                 const int32_t *store_n, int32_t n_graphs, int32_t n_max,
-                 const int32_t *graph_idx, int64_t count, const float *params,
-                 float *emb_out, int32_t *status_out, sg_stream_t stream) {
-  if (!model || count < 0 || n_graphs <= 0 || n_max <= 0) return SG_ERR_ARG;
-  SgGenPlan P;
-  const int rc = embed_plan(model, &P);
-  if (rc != SG_OK) return rc;
-  if (n_max != P.n_max) return SG_ERR_ARG;   // the store's slots are the model's capacity
-  if (count == 0) return SG_OK;
-  if (!store_adj || !store_types || !store_n || !params || !emb_out) return SG_ERR_ARG;
-  // the generic kernel's forward shape: no accumulator, one unit per two graphs
-  const SgGenLaunch L = sg_gen_launch_shape(P, 0, (count + 1) / 2);
-  if (!L.fits()) return SG_ERR_UNSUPPORTED;
-  EmbedArgs A;
-  fill_store_args(A, P, store_adj, store_types, store_n, n_graphs, graph_idx, count, status_out);
-  A.params = params;
-  A.out = emb_out;
-  sg_allow_lds((const void *)sg_embed_kernel, L.lds_bytes);
-  hipLaunchKernelGGL(sg_embed_kernel, dim3(L.blocks), dim3(64 * L.waves_per_block), L.lds_bytes,
-                     (hipStream_t)stream, P, A);
-  return hipGetLastError() == hipSuccess ? SG_OK : SG_ERR_HIP;
-}
 
 int64_t sg_score_grid_workspace_bytes(const sg_model_t *model, int64_t m) {
   SgGenPlan P;

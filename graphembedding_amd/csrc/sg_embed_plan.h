@@ -1,8 +1,10 @@
-// sg_embed_plan.h — what the embed-once translation units share (sg_embed.hip: retrieval,
-// include/siamese_embed.h; sg_embed_train.hip: training, include/siamese_embed_train.h;
-// sg_search.hip: search, include/siamese_search.h; sg_embed_drop.hip: training with
-// graph-keyed dropout, include/siamese_embed_drop.h):
-// the dropout-off plan of a model and the plan that keeps its dropout; the store side of the two embedding kernels (which
+// sg_embed_plan.h — what the embed-once translation units share (sg_embed_nodes.hip: the
+// node stack on single graphs, forward and backward, for include/siamese_embed.h,
+// siamese_embed_train.h and siamese_embed_drop.h; sg_embed.hip: the score grid and top-k of
+// retrieval; sg_embed_train.hip: the grid of training; sg_search.hip: search,
+// include/siamese_search.h):
+// the plans of a model (dropout read as off, dropout refused, dropout kept); the store side
+// of the embedding kernel (which
 // graphs a wavefront takes, what it reports, Â and the types staged in its LDS slice);
 // the NTN score grid's limits, query-chunk split, common kernel arguments, per-query table
 // kernel and MFMA operand helpers; and the key of the top-k selections' total order.
@@ -31,7 +33,7 @@ int embed_plan(const sg_model_t *model, SgGenPlan *P) {
 }
 
 // The plan of the model with its own dropout (keep_prob and the per-layer dropout flags, as
-// the pair paths build it) and the f32 store: graph-keyed masks (sg_embed_drop.hip)
+// the pair paths build it) and the f32 store: graph-keyed masks (sg_embed_nodes.hip, MASK)
 int embed_drop_plan(const sg_model_t *model, SgGenPlan *P) {
   if (!model) return SG_ERR_ARG;
   if (!(model->keep_prob > 0.f && model->keep_prob <= 1.f)) return SG_ERR_ARG;
@@ -40,6 +42,27 @@ int embed_drop_plan(const sg_model_t *model, SgGenPlan *P) {
   sg_model_t m = *model;
   m.adj_dtype = SG_DTYPE_F32;
   return sg_build_plan(&m, P);
+}
+
+// embed_plan with the NTN head the score grid serves, or an SG_ERR_* code
+int grid_plan(const sg_model_t *model, SgGenPlan *P) {
+  const int rc = embed_plan(model, P);
+  if (rc != SG_OK) return rc;
+  if (P->head_kind != SG_NTN || P->D > kGridMaxD || P->K > kGridMaxK) return SG_ERR_UNSUPPORTED;
+  return SG_OK;
+}
+
+// grid_plan / embed_plan of a model without any effective dropout, or an SG_ERR_* code
+// (embed-once training, include/siamese_embed_train.h)
+int train_plan(const sg_model_t *model, SgGenPlan *P, bool grid) {
+  if (!model) return SG_ERR_ARG;
+  const int rc = grid ? grid_plan(model, P) : embed_plan(model, P);
+  if (rc != SG_OK) return rc;
+  if (!(model->keep_prob > 0.f && model->keep_prob <= 1.f)) return SG_ERR_ARG;
+  if (sg_keep_threshold(model->keep_prob) != 65536u)
+    for (int li = 0; li < model->num_layers; ++li)
+      if (model->layers[li].dropout) return SG_ERR_UNSUPPORTED;
+  return SG_OK;
 }
 
 int plan_embed_dim(const SgGenPlan &P) {
@@ -58,7 +81,7 @@ int plan_max_nodes(const SgGenPlan &P) {
 }
 
 // ---------------------------------------------------------------------------
-// The store side of the embedding kernels (sg_embed_kernel, sg_embed_bwd_kernel): one
+// The store side of the embedding kernel (sg_embed_nodes_kernel, sg_embed_nodes.hip): one
 // wavefront runs the node stack on two graphs, the two "sides" of the generic kernel's LDS
 // slice; unit q of a call takes entries 2 q and 2 q + 1 of graph_idx.
 // ---------------------------------------------------------------------------
@@ -137,14 +160,6 @@ __device__ __forceinline__ bool stage_graph_pair(const SgGenPlan &P, const Store
 // NTN score grid: the head the grid serves, its query tables, and what the forward kernel
 // (sg_grid_kernel) and the forward + adjoint kernel (sg_grid_bwd_kernel) set up alike.
 // ---------------------------------------------------------------------------
-// the NTN head the grid serves, or an SG_ERR_* code
-int grid_plan(const sg_model_t *model, SgGenPlan *P) {
-  const int rc = embed_plan(model, P);
-  if (rc != SG_OK) return rc;
-  if (P->head_kind != SG_NTN || P->D > kGridMaxD || P->K > kGridMaxK) return SG_ERR_UNSUPPORTED;
-  return SG_OK;
-}
-
 int grid_dp(const SgGenPlan &P) { return (P.D + 1 + 3) & ~3; }
 
 // Workgroups of a grid kernel: ncb column blocks of 64 database rows times nqc chunks of qb

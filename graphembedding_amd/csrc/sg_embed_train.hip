@@ -1,7 +1,7 @@
 // sg_embed_train.hip — embed-once training (include/siamese_embed_train.h): forward, loss
 // and adjoint of the m x n NTN score grid on v_mfma_f32_16x16x4_f32, the table adjoint
 // that turns the query tables' gradients into the head's parameter gradients and the query
-// embeddings' gradients, and the backward of the generic node stack of single graphs.
+// embeddings' gradients.  (The backward of the node stack, sg_embed_bwd: sg_embed_nodes.hip.)
 //
 // The head (layers.py:282-310) of (query i, database j) is  m_k = [e_j, 1] · Q_i[:, k]
 // (sg_embed_plan.h), r_k = act(m_k), s = ΣU · Σ_k r_k (reference, quirk A1) or Σ_k U_k r_k
@@ -14,7 +14,7 @@
 //   gW[a][b][k] = Σ_i e_i[a] gQ_i[b][k],   gV[k][D+b] = Σ_i gQ_i[b][k],
 //   gV[k][a] = Σ_i e_i[a] gQ_i[D][k],      gbias[k] = Σ_i gQ_i[D][k],
 //   g_emb_q[i][a] = Σ_{b<D,k} W[a][b][k] gQ_i[b][k] + Σ_k V[k][a] gQ_i[D][k].
-// Dropout 0 only: the header states why, train_plan refuses everything else.
+// Dropout 0 only: the header states why, train_plan (sg_embed_plan.h) refuses everything else.
 #include "../../include/siamese_embed_train.h"
 #include "sg_embed_bwd.h"
 #include "sg_mfma.h"
@@ -25,18 +25,6 @@ using sgk::f4;
 
 constexpr int64_t kTrainGridBlocks = 1024;   // workgroups the grid kernel aims for
 constexpr int kBlkStride = 32;               // floats per workgroup partial: gU[16], loss
-
-// grid_plan / embed_plan of a model without any effective dropout, or an SG_ERR_* code
-int train_plan(const sg_model_t *model, SgGenPlan *P, bool grid) {
-  if (!model) return SG_ERR_ARG;
-  const int rc = grid ? grid_plan(model, P) : embed_plan(model, P);
-  if (rc != SG_OK) return rc;
-  if (!(model->keep_prob > 0.f && model->keep_prob <= 1.f)) return SG_ERR_ARG;
-  if (sg_keep_threshold(model->keep_prob) != 65536u)
-    for (int li = 0; li < model->num_layers; ++li)
-      if (model->layers[li].dropout) return SG_ERR_UNSUPPORTED;
-  return SG_OK;
-}
 
 // ---------------------------------------------------------------------------
 // Launch geometry and workspace layout of the grid call (host; independent of the device,
@@ -372,49 +360,6 @@ __global__ void __launch_bounds__(256) sg_grid_head_kernel(HeadArgs A) {
   A.grad_head[e < A.nWV ? e : e + A.K] = acc;   // bias follows U in the parameter vector
 }
 
-// ---------------------------------------------------------------------------
-// Node-stack backward: sg_embed_kernel's staging (stage_graph_pair, sg_embed_plan.h) and
-// forward, the output gradients of the two sides seeded from g_emb, gen_backward_nodes into
-// the workgroup's accumulator G[0 .. head offset).  A side that cannot be embedded (bad id,
-// bad node count, the missing partner of an odd tail) runs the other side's graph with a
-// zero seed: the backward is linear in the seed, so it adds exact zeros.
-// ---------------------------------------------------------------------------
-struct EmbedBwdArgs : StoreArgs {
-  int hoff;
-  const float *params, *g_emb;
-  float *slab;   // [gridDim.x][hoff]
-};
-
-__global__ void __launch_bounds__(256) sg_embed_bwd_kernel(SgGenPlan P, EmbedBwdArgs A) {
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
-  const int gfl = (A.hoff + 3) & ~3;
-  float *G = smem;
-  float *S = smem + gfl + wave * P.wave_floats;
-  for (int i = threadIdx.x; i < gfl; i += blockDim.x) G[i] = 0.f;
-  __syncthreads();
-  const SgGenLayer &last = P.L[P.nl - 1];
-  const int E = last.Rout * last.dout;
-  const int64_t npair = (A.count + 1) >> 1;
-  for (int64_t q = (int64_t)blockIdx.x * nw + wave; q < npair; q += (int64_t)gridDim.x * nw) {
-    int g[2], n[2];
-    bool ok[2], have[2];
-    float *adj;
-    int *types;
-    if (!stage_graph_pair(P, A, S, q, lane, g, n, ok, have, adj, types)) continue;
-    gen_forward_nodes(P, S, A.params, adj, types, n[0], n[1], 0u, lane);
-    float *gcur = S + P.l_g0, *gnext = S + P.l_g1;
-    const float *ge = A.g_emb + (size_t)(2 * q) * E;
-    for (int e = lane; e < 2 * E; e += SG_WAVE) gcur[e] = ok[e >= E] ? ge[e] : 0.f;
-    sg_wsync();
-    gen_backward_nodes(P, S, G, A.params, adj, types, n[0], n[1], 0u, lane, gcur, gnext);
-    sg_wsync();   // the next graphs overwrite the slice
-  }
-  __syncthreads();
-  float *dst = A.slab + (size_t)blockIdx.x * (size_t)A.hoff;
-  for (int i = threadIdx.x; i < A.hoff; i += blockDim.x) dst[i] = G[i];
-}
-
 }  // namespace
 
 extern "C" {
@@ -501,47 +446,6 @@ int32_t sg_score_grid_fwd_bwd(const sg_model_t *model, const float *emb_q, const
   const int ntab = H.nWV + (P.head_bias ? K : 0);
   hipLaunchKernelGGL(sg_grid_head_kernel, dim3((unsigned)((ntab + 255) / 256 + 1)), dim3(256), 0,
                      st, H);
-  return hipGetLastError() == hipSuccess ? SG_OK : SG_ERR_HIP;
-}
-
-int64_t sg_embed_bwd_workspace_bytes(const sg_model_t *model, int64_t count) {
-  SgGenPlan P;
-  if (count < 0 || train_plan(model, &P, false) != SG_OK) return -1;
-  const SgGenLaunch L = embed_bwd_launch(P, count);
-  if (!L.fits()) return -1;
-  return (int64_t)L.blocks * head_offset(P) * 4 + 256;
-}
-
-int32_t sg_embed_bwd(const sg_model_t *model, const float *store_adj,
-                     const int32_t *store_types, const int32_t *store_n, int32_t n_graphs,
-                     int32_t n_max, const int32_t *graph_idx, int64_t count,
-                     const float *params, const float *g_emb, float *grad_out,
-                     int32_t *status_out, void *workspace, sg_stream_t stream) {
-  if (!model || count < 0 || n_graphs <= 0 || n_max <= 0) return SG_ERR_ARG;
-  SgGenPlan P;
-  const int rc = train_plan(model, &P, false);
-  if (rc != SG_OK) return rc;
-  if (n_max != P.n_max) return SG_ERR_ARG;   // the store's slots are the model's capacity
-  if (!grad_out) return SG_ERR_ARG;
-  const int hoff = head_offset(P);
-  hipStream_t st = (hipStream_t)stream;
-  if (count == 0)
-    return hipMemsetAsync(grad_out, 0, (size_t)hoff * 4u, st) == hipSuccess ? SG_OK : SG_ERR_HIP;
-  if (!store_adj || !store_types || !store_n || !params || !g_emb || !workspace)
-    return SG_ERR_ARG;
-  const SgGenLaunch L = embed_bwd_launch(P, count);
-  if (!L.fits()) return SG_ERR_UNSUPPORTED;
-  EmbedBwdArgs A;
-  fill_store_args(A, P, store_adj, store_types, store_n, n_graphs, graph_idx, count, status_out);
-  A.hoff = hoff;
-  A.params = params;
-  A.g_emb = g_emb;
-  A.slab = (float *)workspace;
-  sg_allow_lds((const void *)sg_embed_bwd_kernel, L.lds_bytes);
-  hipLaunchKernelGGL(sg_embed_bwd_kernel, dim3(L.blocks), dim3(64 * L.waves_per_block),
-                     L.lds_bytes, st, P, A);
-  hipLaunchKernelGGL(sg_sum_rows, dim3((unsigned)((hoff + 255) / 256)), dim3(256), 0, st,
-                     (const float *)A.slab, (int64_t)L.blocks, (int64_t)hoff, grad_out);
   return hipGetLastError() == hipSuccess ? SG_OK : SG_ERR_HIP;
 }
 

@@ -1,8 +1,8 @@
 // sg_gen_nodes.h — forward and backward of the generic node-level stack (GCN / Dense /
 // Padding / Average / Attention) for the two graphs a wavefront holds in its LDS slice.
-// Shared by the generic pair kernel (sg_generic.hip) and the embedding kernels (sg_embed.hip,
-// sg_embed_train.hip, sg_embed_drop.hip), so a graph's embedding and its gradient are computed by the code
-// that scores and trains its pairs.
+// Shared by the generic pair kernel (sg_generic.hip) and the embedding kernel
+// (sg_embed_nodes.hip), so a graph's embedding and its gradient are computed by the code that
+// scores and trains its pairs.
 //
 // Reference math: layers.py:91-118 (GCN), 136-140 (Average), 154-160 (Attention),
 // 192-205 (Dense), 223-227 (Padding), 332-338 (sparse dropout).

@@ -40,9 +40,10 @@ struct SgPairRun {
 };
 
 // ---- launch shape of the kernels that run the generic LDS stack ----
-// sg_generic_kernel (sg_generic.hip), sg_embed_kernel (sg_embed.hip), sg_embed_bwd_kernel
-// (sg_embed_train.hip) and the two kernels of sg_embed_drop.hip: a workgroup holds an optional gradient accumulator and one slice of
-// P.wave_floats per wavefront, and each wavefront walks the call's units (pairs of graphs).
+// sg_generic_kernel (sg_generic.hip) and sg_embed_nodes_kernel (sg_embed_nodes.hip, every
+// embed-once call on single graphs): a workgroup holds an optional gradient accumulator and
+// one slice of P.wave_floats per wavefront, and each wavefront walks the call's units (pairs
+// of graphs).
 constexpr size_t kSgGenLdsAim = 81920u;     // 80 KB: four waves shrink until the workgroup fits
 constexpr size_t kSgGenLdsMax = 163840u;    // 160 KB, a CU's LDS: larger workgroups are refused
 constexpr size_t kSgLdsNoAttr = 65536u;     // 64 KB: dynamic LDS above it needs the attribute
