@@ -220,6 +220,20 @@ def lib():
     L.sg_search_topk.argtypes = [pm, vp, vp, c_i64, c_i64, vp, c_i32, c_i32, c_i32, c_i64, vp,
                                  vp, vp, vp]
     L.sg_search_topk.restype = c_i32
+    # embed-once retrieval for graph-store models (include/siamese_web_embed.h)
+    L.sg_web_embed_dim.argtypes = [pm]
+    L.sg_web_embed_dim.restype = c_i32
+    L.sg_web_embed_ld.argtypes = [pm]
+    L.sg_web_embed_ld.restype = c_i32
+    L.sg_web_embed_workspace_bytes.argtypes = [pm, c_i64]
+    L.sg_web_embed_workspace_bytes.restype = c_i64
+    L.sg_web_embed.argtypes = [pm, pc, vp, c_i64, vp, vp, vp, vp, vp]
+    L.sg_web_embed.restype = c_i32
+    L.sg_web_score_grid_workspace_bytes.argtypes = [pm, c_i64]
+    L.sg_web_score_grid_workspace_bytes.restype = c_i64
+    L.sg_web_score_grid.argtypes = [pm, vp, c_i64, vp, c_i64, c_i64, c_i64, vp, c_i32, vp, c_i64,
+                                    vp, vp]
+    L.sg_web_score_grid.restype = c_i32
     _lib = L
     return L
 
@@ -256,6 +270,11 @@ EMBED_DROP_SYMBOLS = ('sg_embed_drop', 'sg_embed_drop_bwd_workspace_bytes', 'sg_
 # the symbols of include/siamese_search.h (embed-once search: score grid + top-k in one call,
 # no m x n matrix; detected by presence, like the training symbols)
 SEARCH_SYMBOLS = ('sg_search_topk_workspace_bytes', 'sg_search_topk')
+
+# the symbols of include/siamese_web_embed.h (embed-once retrieval for graph-store models:
+# embeddings from a CSR store and the NTN score grid at D in [32, 512]; detected by presence)
+WEB_EMBED_SYMBOLS = ('sg_web_embed_dim', 'sg_web_embed_ld', 'sg_web_embed_workspace_bytes',
+                     'sg_web_embed', 'sg_web_score_grid_workspace_bytes', 'sg_web_score_grid')
 
 # class_start entries of sg_pair_order_cls (include/siamese_hip.h SG_FAST_CLASSES_P1)
 FAST_CLASSES_P1 = 5
@@ -639,6 +658,56 @@ def search_topk(m: SgModel, emb_q, emb_db, n_q, n_db, params, apply_final, k, la
                                _ptr(params), int(bool(apply_final)), int(k), int(bool(largest)),
                                int(seg_cols), _ptr(idx_out), _ptr(val_out), _ptr(workspace),
                                _stream(stream)), 'sg_search_topk')
+
+
+_NO_WEB_EMBED = 'model is not on the graph-store path (see embed / score_grid for the others)'
+
+
+def web_embed_dim(m: SgModel) -> int:
+    """Width D of one graph embedding of a graph-store model (sg_web_embed_dim)."""
+    d = int(lib().sg_web_embed_dim(ctypes.byref(m)))
+    if d < 0:
+        raise SiameseHipError('sg_web_embed_dim: ' + _NO_WEB_EMBED)
+    return d
+
+
+def web_embed_ld(m: SgModel) -> int:
+    """Row stride of the embeddings web_embed writes (sg_web_embed_ld)."""
+    ld = int(lib().sg_web_embed_ld(ctypes.byref(m)))
+    if ld < 0:
+        raise SiameseHipError('sg_web_embed_ld: ' + _NO_WEB_EMBED)
+    return ld
+
+
+def web_embed_workspace_bytes(m: SgModel, count: int) -> int:
+    b = int(lib().sg_web_embed_workspace_bytes(ctypes.byref(m), int(count)))
+    if b < 0:
+        raise SiameseHipError('sg_web_embed_workspace_bytes: ' + _NO_WEB_EMBED)
+    return b
+
+
+def web_embed(m: SgModel, store: SgCsrStore, graph_idx, count, params, emb_out, workspace,
+              status=None, stream=None):
+    """sg_web_embed over a CSR store struct (CsrStore.to_device); graph_idx int32 [count]
+    device tensor or None (graphs 0 .. count-1); emb_out [count][web_embed_ld]."""
+    check(lib().sg_web_embed(ctypes.byref(m), ctypes.byref(store), _ptr(graph_idx), int(count),
+                             _ptr(params), _ptr(emb_out), _ptr(status), _ptr(workspace),
+                             _stream(stream)), 'sg_web_embed')
+
+
+def web_score_grid_workspace_bytes(m: SgModel, n_queries: int) -> int:
+    b = int(lib().sg_web_score_grid_workspace_bytes(ctypes.byref(m), int(n_queries)))
+    if b < 0:
+        raise SiameseHipError('sg_web_score_grid_workspace_bytes: ' + _NO_WEB_EMBED)
+    return b
+
+
+def web_score_grid(m: SgModel, emb_q, ld_q, emb_db, ld_db, n_q, n_db, params, apply_final, out,
+                   ld_out, workspace, stream=None):
+    check(lib().sg_web_score_grid(ctypes.byref(m), _ptr(emb_q), int(ld_q), _ptr(emb_db),
+                                  int(ld_db), int(n_q), int(n_db), _ptr(params),
+                                  int(bool(apply_final)), _ptr(out), int(ld_out),
+                                  _ptr(workspace), _stream(stream)), 'sg_web_score_grid')
 
 
 def seed_advance(seed_dev, delta=1, stream=None):

@@ -109,6 +109,15 @@ int sg_web_run(const sg_model_t *m, const sg_csr_store_t *store, const int32_t *
                const float *params, uint64_t seed, const float *y_stats, int add_label,
                float *s_out, float *grad_out, float *loss_out, void *workspace, int64_t chunk,
                bool bwd, hipStream_t st);
+// the NTN head of a path-3 model for the embed-once score grid (sg_web_grid.hip):
+// parameter offsets and head options; SG_OK only for a model sg_model_validate puts on path 3
+struct SgWebHead {
+  int D, Dp, K;
+  int oW, oV, oU, obn;   // obn = -1: no bias
+  int ntn_mode, final_act;
+  float yeta;
+};
+int sg_web_head_plan(const sg_model_t *m, SgWebHead *H);
 
 // ---- layer shapes the fused kernels are written for ----
 constexpr int kSgH1 = 32, kSgH2 = 16, kSgK = 10;   // GCN widths, NTN feature maps

@@ -34,6 +34,7 @@
 #include <mutex>
 #include <vector>
 
+#include "../../include/siamese_web_embed.h"
 #include "sg_mfma.h"
 #include "sg_paths.h"
 
@@ -2074,3 +2075,179 @@ int sg_web_run(const sg_model_t *m, const sg_csr_store_t *store, const int32_t *
   }
   return web_status();
 }
+
+// ===========================================================================
+// Embed-once retrieval for path-3 models (include/siamese_web_embed.h): the node stack of
+// single graphs through the forward instance kernel, unchanged.  Entry c of the call is
+// scheduled as the side-0 instance q = 2 c of a chunk of Cp = count "pairs", so its row
+// lands at X[c] = emb_out[c]; no side-1 instance is scheduled.  Every keep threshold is
+// sg_keep_threshold(1): the masks are all-keep and the pair key plays no part.
+// ===========================================================================
+int sg_web_head_plan(const sg_model_t *m, SgWebHead *H) {
+  WebPlan W;
+  const int rc = web_plan(m, &W);
+  if (rc != SG_OK) return rc;
+  if (!sg_web_lds_ok(m)) return SG_ERR_UNSUPPORTED;
+  if (H) {
+    H->D = W.D; H->Dp = W.Dp; H->K = W.K;
+    H->oW = W.oW; H->oV = W.oV; H->oU = W.oU; H->obn = W.obn;
+    H->ntn_mode = W.ntn_mode; H->final_act = W.final_act; H->yeta = W.yeta;
+  }
+  return SG_OK;
+}
+
+namespace {
+
+// Entry c -> its instance record (first node, nodes, first Â entry, Â entries): inst[2 c]
+// for the instance kernel (inst[2 c + 1], the side never scheduled, is zero) and instc[c]
+// for the size-class sort.  An entry that cannot be embedded (id outside the store:
+// SG_ERR_ARG; node count outside [1, n_max]: SG_ERR_SHAPE, both raised in the device
+// status) gets the empty record: web_embed_zero_kernel writes its row afterwards.
+__global__ void __launch_bounds__(256) web_embed_inst_kernel(const int32_t *__restrict__ gidx,
+                                                             int64_t count, int n_graphs, int n_max,
+                                                             const int32_t *__restrict__ node_off,
+                                                             const int32_t *__restrict__ row_ptr,
+                                                             int4 *__restrict__ inst,
+                                                             int4 *__restrict__ instc,
+                                                             int32_t *__restrict__ status) {
+  const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (c >= count) return;
+  const int64_t id = gidx ? (int64_t)gidx[c] : c;
+  int4 v = make_int4(0, 0, 0, 0);
+  if (id >= 0 && id < n_graphs) {
+    const int o = node_off[id], n = node_off[id + 1] - o;
+    if (n >= 1 && n <= n_max) {
+      const int b = row_ptr[o];
+      v = make_int4(o, n, b, row_ptr[o + n] - b);
+    } else if (status) {
+      atomicExch(status, (int32_t)SG_ERR_SHAPE);
+    }
+  } else if (status) {
+    atomicExch(status, (int32_t)SG_ERR_ARG);
+  }
+  inst[2 * c] = v;
+  inst[2 * c + 1] = make_int4(0, 0, 0, 0);
+  instc[c] = v;
+}
+
+// sorted entry c -> instance q = 2 c
+__global__ void __launch_bounds__(256) web_embed_side0_kernel(int32_t *__restrict__ sorted,
+                                                              int64_t count) {
+  const int64_t x = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (x < count) sorted[x] *= 2;
+}
+
+// rows of the entries with the empty record: zeros (one wavefront per row)
+__global__ void __launch_bounds__(256) web_embed_zero_kernel(const int4 *__restrict__ inst,
+                                                             int64_t count, int ld,
+                                                             float *__restrict__ emb) {
+  const int64_t c = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (c >= count || inst[2 * c].y != 0) return;
+  for (int a = threadIdx.x & 63; a < ld; a += SG_WAVE) emb[c * ld + a] = 0.f;
+}
+
+// workspace of sg_web_embed (4-byte words)
+struct WebEmbWs {
+  int64_t INST, INSTC, ISORT, ICNT, ICLS, total;
+  int nbu;
+};
+
+WebEmbWs web_emb_ws(int64_t count) {
+  WebEmbWs w;
+  if (count < 1) count = 1;
+  int64_t o = 0;
+  auto take = [&](int64_t n) { const int64_t r = o; o += (n + 63) & ~(int64_t)63; return r; };
+  w.nbu = (int)((count + kUnitChunk - 1) / kUnitChunk);
+  w.INST = take(8 * count);     // int4 per instance, two per entry
+  w.INSTC = take(4 * count);    // int4 per entry
+  w.ISORT = take(count);
+  w.ICNT = take((int64_t)kIKeys * w.nbu);
+  w.ICLS = take(kIKeys + 8);
+  w.total = o;
+  return w;
+}
+
+constexpr int64_t kWebEmbMax = (int64_t)1 << 29;   // 2 count instances stay below 2^31
+
+}  // namespace
+
+extern "C" {
+
+int32_t sg_web_embed_dim(const sg_model_t *model) {
+  SgWebHead H;
+  return sg_web_head_plan(model, &H) == SG_OK ? H.D : -1;
+}
+
+int32_t sg_web_embed_ld(const sg_model_t *model) {
+  SgWebHead H;
+  return sg_web_head_plan(model, &H) == SG_OK ? H.Dp : -1;
+}
+
+int64_t sg_web_embed_workspace_bytes(const sg_model_t *model, int64_t count) {
+  if (count < 0 || count > kWebEmbMax || sg_web_head_plan(model, nullptr) != SG_OK) return -1;
+  return web_emb_ws(count).total * 4 + 256;
+}
+
+int32_t sg_web_embed(const sg_model_t *model, const sg_csr_store_t *store,
+                     const int32_t *graph_idx, int64_t count, const float *params,
+                     float *emb_out, int32_t *status_out, void *workspace, sg_stream_t stream) {
+  if (!model || count < 0) return SG_ERR_ARG;
+  WebPlan W;
+  int rc = web_plan(model, &W);
+  if (rc != SG_OK) return rc;
+  if (!sg_web_lds_ok(model)) return SG_ERR_UNSUPPORTED;
+  if (!store || !store->node_off || !store->types || !store->row_ptr || !store->col ||
+      !store->val || store->n_graphs < 0 || store->n_max < 1 || store->n_max > W.D ||
+      store->n_max > model->n_max || store->max_nnz < 0)
+    return SG_ERR_ARG;
+  if (count > kWebEmbMax) return SG_ERR_UNSUPPORTED;
+  if (count == 0) return SG_OK;
+  if (!params || !emb_out || !workspace) return SG_ERR_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  (void)hipGetLastError();   // report only this call's launch errors
+  const WebEmbWs ws = web_emb_ws(count);
+  int32_t *base = (int32_t *)workspace;
+  int4 *inst = (int4 *)(base + ws.INST), *instc = (int4 *)(base + ws.INSTC);
+  int32_t *isort = base + ws.ISORT, *icnt = base + ws.ICNT, *icls = base + ws.ICLS;
+  const unsigned nb256 = (unsigned)((count + 255) / 256);
+  hipLaunchKernelGGL(web_embed_inst_kernel, dim3(nb256), dim3(256), 0, st, graph_idx, count,
+                     store->n_graphs, store->n_max, store->node_off, store->row_ptr, inst, instc,
+                     status_out);
+  // the size-class units of the pair path over the entries (one partition: no id is read)
+  const int n16 = (store->n_max + 15) & ~15;
+  const int cap4 = (n16 / 4) & ~15, cap2 = (n16 / 2) & ~15;
+  hipLaunchKernelGGL(web_icls_count, dim3(ws.nbu), dim3(256), 0, st, (const int4 *)instc,
+                     (const int32_t *)nullptr, count, cap4, cap2, 1, ws.nbu, icnt);
+  hipLaunchKernelGGL(web_icls_scan, dim3(1), dim3(kScanT), 0, st, icnt, ws.nbu, count, 1, icls);
+  hipLaunchKernelGGL(web_icls_scatter, dim3(ws.nbu), dim3(256), 0, st, (const int4 *)instc,
+                     (const int32_t *)nullptr, count, cap4, cap2, 1, ws.nbu,
+                     (const int32_t *)icnt, isort);
+  hipLaunchKernelGGL(web_embed_side0_kernel, dim3(nb256), dim3(256), 0, st, isort, count);
+  GcnArgs G;
+  memset(&G, 0, sizeof(G));
+  G.node_off = store->node_off;
+  G.types = store->types;
+  G.row_ptr = store->row_ptr;
+  G.col = store->col;
+  G.val = store->val;
+  G.inst = inst;
+  G.isorted = isort;
+  G.icls = icls;
+  G.n_pairs = count;
+  G.Cp = count;
+  G.params = params;
+  G.X = emb_out;
+  const uint32_t keep_all = sg_keep_threshold(1.f);
+  G.thr0 = G.thr1 = G.thr2 = G.thr4 = keep_all;
+  G.ik0 = G.ik1 = G.ik2 = G.ik4 = 1.f;
+  G.padv = W.padv;
+  G.d_in = W.d_in; G.D = W.D; G.Dp = W.Dp; G.n_gcn = W.n_gcn; G.n_max = store->n_max;
+  G.max_nnz = store->max_nnz;
+  G.ob0 = W.ob0; G.oW1 = W.oW1; G.ob1 = W.ob1; G.oWd = W.oWd; G.obd = W.obd;
+  if ((rc = gcn_launch(false, W, G, 2 * count, st)) != SG_OK) return rc;
+  hipLaunchKernelGGL(web_embed_zero_kernel, dim3((unsigned)((count + 3) / 4)), dim3(256), 0, st,
+                     (const int4 *)inst, count, W.Dp, emb_out);
+  return web_status();
+}
+
+}  // extern "C"

@@ -529,7 +529,8 @@ class SiameseGCNTNMSE(object):
     def _no_web(self, what):
         if self.is_web:
             raise _lib.SiameseHipError('{}: graph-store (Web) models have no embedding '
-                                       'kernels'.format(what))
+                                       'kernels here; use web_embed / web_score_grid / '
+                                       'topk'.format(what))
 
     @property
     def embed_dim(self) -> int:
@@ -613,6 +614,69 @@ class SiameseGCNTNMSE(object):
         _lib.search_topk(self.sg, q, db, m, n, self.params, final, k, largest, seg_cols, idx,
                          val, ws)
         return idx, val
+
+    # ---- embed-once retrieval for graph-store models (include/siamese_web_embed.h) ----
+    def _only_web(self, what):
+        if not self.is_web:
+            raise _lib.SiameseHipError('{}: the model is not on the graph-store (Web) path; '
+                                       'use embed / score_grid'.format(what))
+
+    @property
+    def web_embed_dim(self) -> int:
+        """Width D of one graph embedding of a graph-store model: the Padding / NTN width."""
+        self._only_web('web_embed_dim')
+        return _lib.web_embed_dim(self.sg)
+
+    def web_embed(self, store, graph_idx=None):
+        """Graph-level embeddings [count][D] (torch, on the device) of the graphs graph_idx
+        (store ids, repeats allowed; None = every graph) of a web.CsrStore.  The tensor is a
+        view of the [count][ld] buffer the kernel writes (ld = D rounded up to 128): it keeps
+        that row stride.  Dropout is off whatever flags.dropout says."""
+        torch = self.torch
+        self._only_web('web_embed')
+        self.check_node_counts(store.n, 'web_embed')
+        idx = None
+        count = len(store)
+        if graph_idx is not None:
+            idx = torch.as_tensor(graph_idx, dtype=torch.int32, device=self.device).reshape(-1)
+            idx = idx.contiguous()
+            count = int(idx.numel())
+        d, ld = _lib.web_embed_dim(self.sg), _lib.web_embed_ld(self.sg)
+        out = torch.empty((count, ld), dtype=torch.float32, device=self.device)
+        status = torch.zeros(1, dtype=torch.int32, device=self.device)
+        ws = torch.empty(_lib.web_embed_workspace_bytes(self.sg, count) // 4 + 1,
+                         dtype=torch.float32, device=self.device)
+        _lib.web_embed(self.sg, store.to_device(self.device), idx, count, self.params, out, ws,
+                       status)
+        _lib.check(int(status.item()), 'sg_web_embed (device status)')
+        return out[:, :d]
+
+    def web_score_grid(self, emb_q, emb_db, final=True):
+        """Scores [m][n] of (query i as graph 1, database j as graph 2) from embeddings
+        (web_embed, or any 2-D float32 tensors [*, D] with unit inner stride: their row
+        strides are passed on): the similarity, or, final=False, the pre-activation score
+        of pred_sim_without_act."""
+        torch = self.torch
+        self._only_web('web_score_grid')
+        d = _lib.web_embed_dim(self.sg)
+
+        def rows(e):
+            e = torch.as_tensor(e, dtype=torch.float32, device=self.device)
+            if e.dim() != 2 or e.shape[1] != d:
+                raise _lib.SiameseHipError('web_score_grid: embeddings must be [*, {}]'.format(d))
+            if e.shape[0] > 1 and (e.stride(1) != 1 or e.stride(0) < d):
+                e = e.contiguous()
+            elif e.shape[0] <= 1 and e.stride(1) != 1:
+                e = e.contiguous()
+            return e, (int(e.stride(0)) if e.shape[0] > 1 else max(d, int(e.stride(0))))
+
+        (q, ld_q), (db, ld_db) = rows(emb_q), rows(emb_db)
+        m, n = int(q.shape[0]), int(db.shape[0])
+        ws = torch.empty(_lib.web_score_grid_workspace_bytes(self.sg, m) // 4 + 1,
+                         dtype=torch.float32, device=self.device)
+        out = torch.empty((m, n), dtype=torch.float32, device=self.device)
+        _lib.web_score_grid(self.sg, q, ld_q, db, ld_db, m, n, self.params, final, out, n, ws)
+        return out
 
     # ---- embed-once training (include/siamese_embed_train.h: dropout 0 only;
     # include/siamese_embed_drop.h: dropout='graph', masks keyed per graph) ----

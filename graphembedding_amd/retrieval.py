@@ -16,19 +16,24 @@ from .packer import GraphStore
 
 class EmbeddingIndex(object):
     def __init__(self, model, graphs: Sequence):
-        """model: SiameseGCNTNMSE (not a graph-store model); graphs: ModelGraphs."""
+        """model: SiameseGCNTNMSE; graphs: ModelGraphs.  A graph-store (Web) model embeds
+        from a CSR store and scores with the large-D grid (include/siamese_web_embed.h)."""
         self.model = model
         self.n = len(graphs)
         self.embeddings = self._embed(graphs)       # torch float32 [n][embed_dim], device
 
     def _embed(self, graphs: Sequence):
         m = self.model
+        if m.is_web:
+            from .web import CsrStore
+            return m.web_embed(CsrStore(list(graphs), m.input_dim, m.n_max))
         return m.embed(GraphStore(list(graphs), m.n_max, m.input_dim))
 
     def scores(self, query_graphs: Sequence, final: bool = True):
         """Similarity matrix [m][n] (torch, device): row i = query i as graph 1 against
         every indexed graph as graph 2; final=False gives the pre-activation scores."""
-        return self.model.score_grid(self._embed(query_graphs), self.embeddings, final=final)
+        grid = self.model.web_score_grid if self.model.is_web else self.model.score_grid
+        return grid(self._embed(query_graphs), self.embeddings, final=final)
 
     def topk(self, query_graphs: Sequence, k: int, largest: bool = True):
         """(idx int32 [m][k], sims [m][k]): the k most similar indexed graphs per query,
@@ -38,5 +43,10 @@ class EmbeddingIndex(object):
     def search(self, query_graphs: Sequence, k: int, largest: bool = True):
         """What topk returns, from one fused call that keeps a running top-k per query on
         the chip and never holds the [m][n] similarity matrix (include/siamese_search.h):
-        the way to query an index too large for `scores`."""
+        the way to query an index too large for `scores`.  Not for graph-store (Web) models:
+        use topk."""
+        if self.model.is_web:
+            from ._lib import SiameseHipError
+            raise SiameseHipError('EmbeddingIndex.search: graph-store (Web) models have no fused '
+                                  'search; use topk')
         return self.model.search(self._embed(query_graphs), self.embeddings, k, largest=largest)

@@ -129,12 +129,18 @@ def _test_embed(data, model, f, evaluator, verbose):
         raise RuntimeError('Unknown test_time {}'.format(time_mode))
     graphs = [data.test_data.get_graph(i) for i in range(m)] + \
         [data.get_orig_train_graph(j) for j in range(n)]   # permuted after training (A6)
-    store = GraphStore(graphs, model.n_max, model.input_dim)
+    if model.is_web:   # graph-store models: CSR store, include/siamese_web_embed.h
+        from .web import CsrStore
+        store = CsrStore(graphs, model.input_dim, model.n_max)
+        embed, grid = model.web_embed, model.web_score_grid
+    else:
+        store = GraphStore(graphs, model.n_max, model.input_dim)
+        embed, grid = model.embed, model.score_grid
     store.to_device(model.device)
     _sync()
     t0 = _time.time()
-    emb = model.embed(store)
-    s = model.score_grid(emb[:m], emb[m:], final=True)
+    emb = embed(store)
+    s = grid(emb[:m], emb[m:], final=True)
     _sync()
     elapsed = _time.time() - t0
     sims = s.cpu().numpy().astype(np.float64)

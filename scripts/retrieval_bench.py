@@ -22,6 +22,16 @@ sg_topk_rows of the same build on synthetic embeddings,
 with both ways' workspace bytes.  The two ways must agree bit for bit before they are timed.
 "fused_wins": the fused median is below the two-call median by more than the larger
 max - min of the repeats.
+
+    python scripts/retrieval_bench.py --web [--repeats 3] [--out FILE.json]
+
+runs leg (e) alone: a graph-store (Web) model at D = 512, K = 16 on synthetic graphs of 200
+to 512 nodes (768 distinct graphs; the 4096 database entries repeat 512 of them),
+  (e1) 256 x 256 and (e2) 256 x 4096: sg_web_embed of the m + n entries + sg_web_score_grid
+       (and the parts alone) against the only other way to fill the matrix, sg_web_forward
+       over all m·n pairs of the dropout-0 model,
+with the grid's f32 MFMA rate (2·Dq·16 FLOP per pair as issued) against the 157.3 TFLOP/s
+peak.  The two ways must agree within 1e-4 before they are timed.
 """
 import json
 import os
@@ -126,9 +136,107 @@ def search_leg():
             f.write(line + '\n')
 
 
+def web_leg():
+    """Leg (e): sg_web_embed + sg_web_score_grid against sg_web_forward over all pairs."""
+    import torch
+    from graphembedding_amd import _lib
+    from graphembedding_amd.config import Flags
+    from graphembedding_amd.data import synthetic_graph
+    from graphembedding_amd.graphs import ModelGraph, NodeFeatureOneHotEncoder
+    from graphembedding_amd.model_mse import SiameseGCNTNMSE
+    from graphembedding_amd.web import CsrStore
+    if not torch.cuda.is_available():
+        raise SystemExit('retrieval_bench needs a GPU (there is no CPU fallback)')
+    dev = torch.device('cuda', 0)
+    repeats = _arg('--repeats', 3)
+    D, K, M, G = 512, 16, 256, 768
+    rng = np.random.default_rng(0)
+    graphs = [synthetic_graph(rng, int(rng.integers(200, D + 1)), gid, 29, p_extra=0.012)
+              for gid in range(G)]
+    enc = NodeFeatureOneHotEncoder(graphs, 'type').pin_sorted()
+    mgs = [ModelGraph(g, enc) for g in graphs]
+    flags = Flags(dropout=0.0,
+                  layer_3='Padding:max_in_dims={},padding_value=0'.format(D),
+                  layer_4='NTN:input_dim={},feature_map_dim={},inneract=relu,dropout=True,'
+                          'bias=True'.format(D, K))
+    model = SiameseGCNTNMSE(enc.input_dim(), flags, device=dev, n_max=D)
+    assert model.is_web
+    store = CsrStore(mgs, enc.input_dim(), D)
+    sdev = store.to_device(dev)
+    ld, dq = _lib.web_embed_ld(model.sg), (D + 1 + 3) // 4 * 4
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    cases, info = [], {}
+    for name, n, iters_grid, iters_pair in (('e1_256x256', 256, 10, 3), ('e2_256x4096', 4096, 5, 1)):
+        ids = np.concatenate([np.arange(M), M + np.arange(n) % (G - M)]).astype(np.int32)
+        idx = torch.from_numpy(ids).to(dev)
+        cnt = M + n
+        emb = torch.empty((cnt, ld), dtype=torch.float32, device=dev)
+        ws_e = torch.empty(_lib.web_embed_workspace_bytes(model.sg, cnt) // 4 + 1,
+                           dtype=torch.float32, device=dev)
+        ws_g = torch.empty(_lib.web_score_grid_workspace_bytes(model.sg, M) // 4 + 1,
+                           dtype=torch.float32, device=dev)
+        out = torch.empty((M, n), dtype=torch.float32, device=dev)
+        pairs = torch.from_numpy(np.stack([np.repeat(ids[:M], n), np.tile(ids[M:], M)],
+                                          axis=1).astype(np.int32)).to(dev)
+        chunk = 8192
+        batch = model.web_batch(store, pairs, np.zeros(M * n, np.float32), chunk=chunk)
+        ws_p = model.web_workspace(chunk, M * n)
+        s = torch.empty(M * n, dtype=torch.float32, device=dev)
+
+        def embed(idx=idx, cnt=cnt, emb=emb, ws_e=ws_e):
+            _lib.web_embed(model.sg, sdev, idx, cnt, model.params, emb, ws_e, status)
+
+        def grid(emb=emb, n=n, out=out, ws_g=ws_g):
+            _lib.web_score_grid(model.sg, emb[:M], ld, emb[M:], ld, M, n, model.params, False, out,
+                                n, ws_g)
+
+        def embed_grid(embed=embed, grid=grid):
+            embed()
+            grid()
+
+        def pairwise(batch=batch, s=s, ws_p=ws_p, chunk=chunk):
+            _lib.web_forward(model.sg, sdev, batch.pairs, batch.n_pairs, 0, model.params, 1, s,
+                             ws_p, chunk)
+
+        embed_grid()
+        pairwise()
+        torch.cuda.synchronize()
+        assert int(status.item()) == 0
+        err = float((out.reshape(-1) - s).abs().max().item())
+        assert err <= 1e-4 * max(1.0, float(s.abs().max().item())), err
+        cases += [(name + '/embed_grid', embed_grid, iters_grid), (name + '/embed', embed, iters_grid),
+                  (name + '/grid', grid, iters_grid), (name + '/pairwise', pairwise, iters_pair)]
+        info[name] = dict(m=M, n=n, max_abs_score_diff=err, max_abs_score=float(s.abs().max().item()))
+    for _, fn, _ in cases:       # warm-up of every shape
+        timed(fn, 1)
+    ms = {k: [] for k, _, _ in cases}
+    for _ in range(repeats):     # alternated
+        for k, fn, iters in cases:
+            ms[k].append(timed(fn, iters))
+    for name, d in info.items():
+        med = {k: float(np.median(ms[name + '/' + k])) for k in ('embed_grid', 'embed', 'grid',
+                                                                 'pairwise')}
+        flop = 2.0 * dq * 16 * d['m'] * d['n']
+        d.update(msec={k: ms[name + '/' + k] for k in med}, msec_median=med,
+                 pairwise_over_embed_grid=med['pairwise'] / med['embed_grid'],
+                 grid_mfma_tflops=flop / (med['grid'] * 1e-3) / 1e12,
+                 grid_mfma_fraction_of_157_3=flop / (med['grid'] * 1e-3) / 1e12 / 157.3)
+    res = dict(leg='web', D=D, K=K, distinct_graphs=G, nodes='200..512', repeats=repeats,
+               cases=info, device=torch.cuda.get_device_name(0))
+    line = json.dumps(res)
+    print(line)
+    out = _arg('--out', '')
+    if out:
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+        with open(out, 'w') as f:
+            f.write(line + '\n')
+
+
 def main():
     if '--search' in sys.argv[1:]:
         return search_leg()
+    if '--web' in sys.argv[1:]:
+        return web_leg()
     import torch
     from graphembedding_amd import _lib
     from graphembedding_amd.allpairs import load_graph_set
