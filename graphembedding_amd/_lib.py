@@ -234,6 +234,12 @@ def lib():
     L.sg_web_score_grid.argtypes = [pm, vp, c_i64, vp, c_i64, c_i64, c_i64, vp, c_i32, vp, c_i64,
                                     vp, vp]
     L.sg_web_score_grid.restype = c_i32
+    # embed-once search for graph-store models (include/siamese_web_search.h)
+    L.sg_web_search_topk_workspace_bytes.argtypes = [pm, c_i64, c_i64, c_i32, c_i64]
+    L.sg_web_search_topk_workspace_bytes.restype = c_i64
+    L.sg_web_search_topk.argtypes = [pm, vp, c_i64, vp, c_i64, c_i64, c_i64, vp, c_i32, c_i32,
+                                     c_i32, c_i64, vp, vp, vp, vp]
+    L.sg_web_search_topk.restype = c_i32
     _lib = L
     return L
 
@@ -275,6 +281,10 @@ SEARCH_SYMBOLS = ('sg_search_topk_workspace_bytes', 'sg_search_topk')
 # embeddings from a CSR store and the NTN score grid at D in [32, 512]; detected by presence)
 WEB_EMBED_SYMBOLS = ('sg_web_embed_dim', 'sg_web_embed_ld', 'sg_web_embed_workspace_bytes',
                      'sg_web_embed', 'sg_web_score_grid_workspace_bytes', 'sg_web_score_grid')
+
+# the symbols of include/siamese_web_search.h (embed-once search for graph-store models: the
+# large-D score grid + top-k in one call, no m x n matrix; detected by presence)
+WEB_SEARCH_SYMBOLS = ('sg_web_search_topk_workspace_bytes', 'sg_web_search_topk')
 
 # class_start entries of sg_pair_order_cls (include/siamese_hip.h SG_FAST_CLASSES_P1)
 FAST_CLASSES_P1 = 5
@@ -708,6 +718,27 @@ def web_score_grid(m: SgModel, emb_q, ld_q, emb_db, ld_db, n_q, n_db, params, ap
                                   int(ld_db), int(n_q), int(n_db), _ptr(params),
                                   int(bool(apply_final)), _ptr(out), int(ld_out),
                                   _ptr(workspace), _stream(stream)), 'sg_web_score_grid')
+
+
+def web_search_workspace_bytes(m: SgModel, n_q: int, n_db: int, k: int, seg_cols: int = 0) -> int:
+    b = int(lib().sg_web_search_topk_workspace_bytes(ctypes.byref(m), int(n_q), int(n_db),
+                                                     int(k), int(seg_cols)))
+    if b < 0:
+        raise SiameseHipError('sg_web_search_topk_workspace_bytes: the search serves graph-store '
+                              'models with feature_map_dim <= 16, 1 <= k <= min(n, 64) and '
+                              'seg_cols = 0 or a positive multiple of 64')
+    return b
+
+
+def web_search_topk(m: SgModel, emb_q, ld_q, emb_db, ld_db, n_q, n_db, params, apply_final, k,
+                    largest, seg_cols, idx_out, val_out, workspace, stream=None):
+    """sg_web_search_topk: what web_score_grid + topk_rows return, without the [n_q][n_db]
+    matrix."""
+    check(lib().sg_web_search_topk(ctypes.byref(m), _ptr(emb_q), int(ld_q), _ptr(emb_db),
+                                   int(ld_db), int(n_q), int(n_db), _ptr(params),
+                                   int(bool(apply_final)), int(k), int(bool(largest)),
+                                   int(seg_cols), _ptr(idx_out), _ptr(val_out), _ptr(workspace),
+                                   _stream(stream)), 'sg_web_search_topk')
 
 
 def seed_advance(seed_dev, delta=1, stream=None):

@@ -6,15 +6,14 @@
 #include "../../include/siamese_search.h"
 #include "sg_embed_plan.h"
 #include "sg_mfma.h"
+#include "sg_search_lists.h"
 
 namespace {
 
 using sgk::f4;
 
-constexpr int kTopkMax = 64;            // one list entry per lane
 constexpr int64_t kSegMin = 1024;       // the library's own segment choice lies in
 constexpr int64_t kSegMax = 65536;      // [kSegMin, kSegMax] columns
-constexpr int kListBytes = 12;          // a list entry: 64-bit key + the value's bits
 constexpr int kListLds = 32768;         // LDS for the lists of a workgroup's queries
 
 // ---------------------------------------------------------------------------
@@ -75,52 +74,8 @@ int search_plan(const sg_model_t *model, int64_t m, int64_t n, int32_t k, int64_
   return SG_OK;
 }
 
-// ---------------------------------------------------------------------------
-// The running top-k of one query: k keys in ascending order (best first) with the value
-// bits beside them (a key does not keep the sign of a zero or a NaN's payload, and the
-// two-call path returns the stored float).  Between column blocks a list rests in the
-// wavefront's LDS; only its last key, the threshold, is read per block.  When a block has
-// keys below the threshold the list is taken into registers, lane r the r-th entry (lanes
-// >= k the all-ones sentinel), and the hits are inserted by rank in ascending lane order,
-// a wave-uniform loop:  pos = popcount(ballot(entry < new)), lanes above pos take their
-// lower neighbour's entry, lane pos takes the new one.
-// ---------------------------------------------------------------------------
-__device__ __forceinline__ uint64_t readlane64(uint64_t v, int l) {
-  const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, l);
-  const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), l);
-  return ((uint64_t)hi << 32) | lo;
-}
-
-__device__ __forceinline__ void list_insert(uint64_t *lk, float *lv, int k, int lane,
-                                            uint64_t key, float s, uint64_t hits,
-                                            uint64_t thr) {
-  uint64_t mk = lane < k ? lk[lane] : ~0ull;
-  float mv = lane < k ? lv[lane] : 0.f;
-  while (hits) {
-    const int src = __builtin_ctzll(hits);
-    hits &= hits - 1;
-    const uint64_t nk = readlane64(key, src);
-    if (nk >= thr) continue;   // an earlier hit of this block lowered the threshold past it
-    const float nv = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(s), src));
-    const int pos = __popcll(__ballot(mk < nk));   // < k: nk is below entry k - 1
-    const uint64_t uk = __shfl_up(mk, 1, 64);
-    const float uv = __shfl_up(mv, 1, 64);
-    if (lane > pos) {
-      mk = uk;
-      mv = uv;
-    }
-    if (lane == pos) {
-      mk = nk;
-      mv = nv;
-    }
-    if (lane >= k) mk = ~0ull;   // what falls off the list
-    thr = readlane64(mk, k - 1);
-  }
-  if (lane < k) {
-    lk[lane] = mk;
-    lv[lane] = mv;
-  }
-}
+// The running top-k list of a query (list_insert) and the merge of the segments' candidate
+// lists (sg_search_merge_kernel) are shared with sg_web_search.hip: sg_search_lists.h.
 
 // ---------------------------------------------------------------------------
 // A workgroup owns one segment of the database and one chunk of qb queries.  As in
@@ -210,47 +165,6 @@ __global__ void __launch_bounds__(256) sg_search_kernel(SearchArgs A) {
       const int64_t o = (sgm * A.m + i) * k + lane;
       A.ckey[o] = key;
       A.cval[o] = val;
-    }
-  }
-}
-
-// ---------------------------------------------------------------------------
-// Merge: one wavefront per query picks the k smallest of its nseg · k candidate keys by
-// sg_topk_kernel's selection rounds (keys of distinct columns differ, so "the smallest key
-// above the previous round's" is exact; the sentinels of a short segment are above every
-// key and k <= n candidates are real).  The lane that held a round's winner writes it.
-// ---------------------------------------------------------------------------
-__global__ void __launch_bounds__(64) sg_search_merge_kernel(const uint64_t *__restrict__ ckey,
-                                                             const float *__restrict__ cval,
-                                                             int64_t m, int nseg, int k,
-                                                             int32_t *__restrict__ idx,
-                                                             float *__restrict__ val) {
-  const int lane = threadIdx.x;
-  const int64_t i = blockIdx.x;
-  const uint32_t total = (uint32_t)nseg * (uint32_t)k;   // <= 2^23 segments · 64
-  uint64_t prev = 0;   // below every key
-  for (int r = 0; r < k; ++r) {
-    uint64_t best = ~0ull;
-    int64_t bpos = 0;
-    for (uint32_t t = lane; t < total; t += SG_WAVE) {
-      const uint32_t sgm = t / (uint32_t)k, e = t - sgm * (uint32_t)k;
-      const int64_t pos = ((int64_t)sgm * m + i) * k + e;
-      const uint64_t key = ckey[pos];
-      if (key > prev && key < best) {
-        best = key;
-        bpos = pos;
-      }
-    }
-    uint64_t win = best;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const uint64_t other = __shfl_xor(win, o, 64);
-      win = other < win ? other : win;
-    }
-    prev = win;
-    if (best == win) {   // one lane: the keys are distinct
-      idx[i * k + r] = (int32_t)(uint32_t)win;
-      if (val) val[i * k + r] = cval[bpos];
     }
   }
 }

@@ -530,7 +530,7 @@ class SiameseGCNTNMSE(object):
         if self.is_web:
             raise _lib.SiameseHipError('{}: graph-store (Web) models have no embedding '
                                        'kernels here; use web_embed / web_score_grid / '
-                                       'topk'.format(what))
+                                       'web_search / topk'.format(what))
 
     @property
     def embed_dim(self) -> int:
@@ -658,25 +658,49 @@ class SiameseGCNTNMSE(object):
         of pred_sim_without_act."""
         torch = self.torch
         self._only_web('web_score_grid')
-        d = _lib.web_embed_dim(self.sg)
-
-        def rows(e):
-            e = torch.as_tensor(e, dtype=torch.float32, device=self.device)
-            if e.dim() != 2 or e.shape[1] != d:
-                raise _lib.SiameseHipError('web_score_grid: embeddings must be [*, {}]'.format(d))
-            if e.shape[0] > 1 and (e.stride(1) != 1 or e.stride(0) < d):
-                e = e.contiguous()
-            elif e.shape[0] <= 1 and e.stride(1) != 1:
-                e = e.contiguous()
-            return e, (int(e.stride(0)) if e.shape[0] > 1 else max(d, int(e.stride(0))))
-
-        (q, ld_q), (db, ld_db) = rows(emb_q), rows(emb_db)
+        (q, ld_q), (db, ld_db) = (self._web_rows(e, 'web_score_grid') for e in (emb_q, emb_db))
         m, n = int(q.shape[0]), int(db.shape[0])
         ws = torch.empty(_lib.web_score_grid_workspace_bytes(self.sg, m) // 4 + 1,
                          dtype=torch.float32, device=self.device)
         out = torch.empty((m, n), dtype=torch.float32, device=self.device)
         _lib.web_score_grid(self.sg, q, ld_q, db, ld_db, m, n, self.params, final, out, n, ws)
         return out
+
+    def _web_rows(self, e, what):
+        """(tensor, row stride) of embeddings [*, D] as the web_* grid calls take them: a
+        tensor with unit inner stride and a row stride >= D is passed on as it is (the
+        web_embed view with its stride of 128 or more), anything else is copied."""
+        torch = self.torch
+        d = _lib.web_embed_dim(self.sg)
+        e = torch.as_tensor(e, dtype=torch.float32, device=self.device)
+        if e.dim() != 2 or e.shape[1] != d:
+            raise _lib.SiameseHipError('{}: embeddings must be [*, {}]'.format(what, d))
+        if e.shape[0] > 1 and (e.stride(1) != 1 or e.stride(0) < d):
+            e = e.contiguous()
+        elif e.shape[0] <= 1 and e.stride(1) != 1:
+            e = e.contiguous()
+        return e, (int(e.stride(0)) if e.shape[0] > 1 else max(d, int(e.stride(0))))
+
+    def web_search(self, emb_q, emb_db, k, largest=True, final=True, seg_cols=0):
+        """(idx int32 [m][k], values [m][k]): topk(web_score_grid(emb_q, emb_db, final), k,
+        largest), bit for bit, from one fused call that never holds the [m][n] scores
+        (include/siamese_web_search.h).  Row strides are handled as web_score_grid handles
+        them.  seg_cols: database columns per workgroup, 0 = the library's choice; the result
+        does not depend on it."""
+        torch = self.torch
+        self._only_web('web_search')
+        (q, ld_q), (db, ld_db) = (self._web_rows(e, 'web_search') for e in (emb_q, emb_db))
+        m, n = int(q.shape[0]), int(db.shape[0])
+        nbytes = _lib.web_search_workspace_bytes(self.sg, m, n, k, seg_cols)
+        ws = getattr(self, '_web_search_ws', None)   # the last workspace, kept while it fits
+        if ws is None or ws.numel() * 4 < nbytes or ws.device != q.device:
+            ws = torch.empty(nbytes // 4 + 1, dtype=torch.float32, device=self.device)
+            self._web_search_ws = ws
+        idx = torch.empty((m, int(k)), dtype=torch.int32, device=self.device)
+        val = torch.empty((m, int(k)), dtype=torch.float32, device=self.device)
+        _lib.web_search_topk(self.sg, q, ld_q, db, ld_db, m, n, self.params, final, k, largest,
+                             seg_cols, idx, val, ws)
+        return idx, val
 
     # ---- embed-once training (include/siamese_embed_train.h: dropout 0 only;
     # include/siamese_embed_drop.h: dropout='graph', masks keyed per graph) ----

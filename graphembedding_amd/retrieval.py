@@ -44,9 +44,16 @@ class EmbeddingIndex(object):
         """What topk returns, from one fused call that keeps a running top-k per query on
         the chip and never holds the [m][n] similarity matrix (include/siamese_search.h):
         the way to query an index too large for `scores`.  Not for graph-store (Web) models:
-        use topk."""
+        use `nearest`, which runs the fused search of either kind of model."""
         if self.model.is_web:
             from ._lib import SiameseHipError
-            raise SiameseHipError('EmbeddingIndex.search: graph-store (Web) models have no fused '
-                                  'search; use topk')
+            raise SiameseHipError('EmbeddingIndex.search: graph-store (Web) models are served '
+                                  'by nearest (fused) or topk')
         return self.model.search(self._embed(query_graphs), self.embeddings, k, largest=largest)
+
+    def nearest(self, query_graphs: Sequence, k: int, largest: bool = True):
+        """What topk returns, bit for bit, from the fused search of the model's kind:
+        web_search on a graph-store (Web) model (include/siamese_web_search.h), search on
+        every other (include/siamese_search.h).  Neither holds the [m][n] matrix."""
+        fused = self.model.web_search if self.model.is_web else self.model.search
+        return fused(self._embed(query_graphs), self.embeddings, k, largest=largest)

@@ -32,6 +32,11 @@ to 512 nodes (768 distinct graphs; the 4096 database entries repeat 512 of them)
        over all m·n pairs of the dropout-0 model,
 with the grid's f32 MFMA rate (2·Dq·16 FLOP per pair as issued) against the 157.3 TFLOP/s
 peak.  The two ways must agree within 1e-4 before they are timed.
+  (e3) the fused sg_web_search_topk against sg_web_score_grid + sg_topk_rows of the same
+       build on synthetic dense embeddings, for the shapes and k of leg (d): 4096 x 4096,
+       k = 10; 256 x 1,048,576, k = 10 and k = 64 (the two-call way holds its 1 GiB matrix),
+with both ways' workspace bytes and the segment and query-chunk sizes the library chose.
+The two ways must agree bit for bit before they are timed; "fused_wins" as in leg (d).
 """
 import json
 import os
@@ -136,8 +141,88 @@ def search_leg():
             f.write(line + '\n')
 
 
+def web_search_plan(m, n, k, cus):
+    """(seg, qb) the library picks at seg_cols = 0: web_search_plan of sg_web_search.hip,
+    transcribed to report them (the call itself takes nothing from here)."""
+    target, max_qc = 2 * cus, ((m + 3) // 4 if m > 4 else 1)
+    seg = 4096
+    while seg < 1024 * k:
+        seg <<= 1
+    while seg > 1024 and -(-n // seg) * max_qc < target:
+        seg >>= 1
+    if seg > n:
+        seg = (n + 63) & ~63
+    nqc = min(max_qc, -(-target // -(-n // seg)))
+    qb = max(4, min((12288 // (12 * k)) & ~3, (-(-m // nqc) + 3) & ~3))
+    return seg, qb
+
+
+def web_search_cases(model, dev, D):
+    """Leg (e3): (cases, info) of sg_web_search_topk against sg_web_score_grid +
+    sg_topk_rows on synthetic embeddings, dense and signed, uniform in (-1, 1)."""
+    import torch
+    from graphembedding_amd import _lib
+    cus = int(torch.cuda.get_device_properties(dev).multi_processor_count)
+    shapes = [('e3_4096x4096_k10', 4096, 4096, 10, 5), ('e3_256x1048576_k10', 256, 1 << 20, 10, 2),
+              ('e3_256x1048576_k64', 256, 1 << 20, 64, 2)]
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(0)
+    emb = {rows: torch.rand((rows, D), generator=gen, dtype=torch.float32, device=dev) * 2 - 1
+           for rows in (256, 4096, 1 << 20)}
+    cases, info = [], {}
+    for name, m, n, k, iters in shapes:
+        q, db = emb[m], emb[n]
+        ws2_bytes = _lib.web_score_grid_workspace_bytes(model.sg, m)
+        ws1_bytes = _lib.web_search_workspace_bytes(model.sg, m, n, k, 0)
+        ws2 = torch.empty(ws2_bytes // 4 + 1, dtype=torch.float32, device=dev)
+        ws1 = torch.empty(ws1_bytes // 4 + 1, dtype=torch.float32, device=dev)
+        out = torch.empty((m, n), dtype=torch.float32, device=dev)
+        idx2 = torch.empty((m, k), dtype=torch.int32, device=dev)
+        val2 = torch.empty((m, k), dtype=torch.float32, device=dev)
+        idx1, val1 = torch.empty_like(idx2), torch.empty_like(val2)
+
+        def grid_only(q=q, db=db, m=m, n=n, out=out, ws2=ws2):
+            _lib.web_score_grid(model.sg, q, D, db, D, m, n, model.params, True, out, n, ws2)
+
+        def two_call(grid_only=grid_only, m=m, n=n, k=k, out=out, idx2=idx2, val2=val2):
+            grid_only()
+            _lib.topk_rows(out, m, n, n, k, True, idx2, val2)
+
+        def fused(q=q, db=db, m=m, n=n, k=k, ws1=ws1, idx1=idx1, val1=val1):
+            _lib.web_search_topk(model.sg, q, D, db, D, m, n, model.params, True, k, True, 0,
+                                 idx1, val1, ws1)
+
+        two_call()
+        fused()
+        torch.cuda.synchronize()
+        assert torch.equal(idx1, idx2) and torch.equal(val1.view(torch.int32),
+                                                       val2.view(torch.int32)), name
+        cases += [(name + '/fused', fused, iters), (name + '/two_call', two_call, iters),
+                  (name + '/grid_only', grid_only, iters)]
+        seg, qb = web_search_plan(m, n, k, cus)
+        info[name] = dict(m=m, n=n, k=k, iters=iters, seg_cols_chosen=seg, qb=qb,
+                          fused_workspace_bytes=ws1_bytes, two_call_workspace_bytes=ws2_bytes,
+                          two_call_matrix_bytes=m * n * 4, bitwise_equal=True)
+    return cases, info
+
+
+def web_search_summary(info, ms, dq):
+    for name, d in info.items():
+        f, t, g = (ms[name + '/' + x] for x in ('fused', 'two_call', 'grid_only'))
+        spread = max(max(f) - min(f), max(t) - min(t))
+        flop = 2.0 * dq * 16 * d['m'] * d['n']
+        d.update(msec_fused=f, msec_two_call=t, msec_grid_only=g,
+                 median_fused=float(np.median(f)), median_two_call=float(np.median(t)),
+                 median_grid_only=float(np.median(g)), larger_spread=spread,
+                 two_call_over_fused=float(np.median(t) / np.median(f)),
+                 fused_over_grid_only=float(np.median(f) / np.median(g)),
+                 fused_wins=bool(np.median(t) - np.median(f) > spread),
+                 fused_mfma_tflops=flop / (float(np.median(f)) * 1e-3) / 1e12)
+
+
 def web_leg():
-    """Leg (e): sg_web_embed + sg_web_score_grid against sg_web_forward over all pairs."""
+    """Leg (e): sg_web_embed + sg_web_score_grid against sg_web_forward over all pairs, and
+    the fused sg_web_search_topk against sg_web_score_grid + sg_topk_rows."""
     import torch
     from graphembedding_amd import _lib
     from graphembedding_amd.config import Flags
@@ -207,12 +292,15 @@ def web_leg():
         cases += [(name + '/embed_grid', embed_grid, iters_grid), (name + '/embed', embed, iters_grid),
                   (name + '/grid', grid, iters_grid), (name + '/pairwise', pairwise, iters_pair)]
         info[name] = dict(m=M, n=n, max_abs_score_diff=err, max_abs_score=float(s.abs().max().item()))
+    search_cases, search_info = web_search_cases(model, dev, D)
+    cases += search_cases
     for _, fn, _ in cases:       # warm-up of every shape
         timed(fn, 1)
     ms = {k: [] for k, _, _ in cases}
     for _ in range(repeats):     # alternated
         for k, fn, iters in cases:
             ms[k].append(timed(fn, iters))
+    web_search_summary(search_info, ms, dq)
     for name, d in info.items():
         med = {k: float(np.median(ms[name + '/' + k])) for k in ('embed_grid', 'embed', 'grid',
                                                                  'pairwise')}
@@ -222,7 +310,7 @@ def web_leg():
                  grid_mfma_tflops=flop / (med['grid'] * 1e-3) / 1e12,
                  grid_mfma_fraction_of_157_3=flop / (med['grid'] * 1e-3) / 1e12 / 157.3)
     res = dict(leg='web', D=D, K=K, distinct_graphs=G, nodes='200..512', repeats=repeats,
-               cases=info, device=torch.cuda.get_device_name(0))
+               cases=info, search_cases=search_info, device=torch.cuda.get_device_name(0))
     line = json.dumps(res)
     print(line)
     out = _arg('--out', '')
