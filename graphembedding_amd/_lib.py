@@ -240,6 +240,17 @@ def lib():
     L.sg_web_search_topk.argtypes = [pm, vp, c_i64, vp, c_i64, c_i64, c_i64, vp, c_i32, c_i32,
                                      c_i32, c_i64, vp, vp, vp, vp]
     L.sg_web_search_topk.restype = c_i32
+    # embed-once training for graph-store models (include/siamese_web_embed_train.h)
+    L.sg_web_score_grid_bwd_workspace_bytes.argtypes = [pm, c_i64, c_i64]
+    L.sg_web_score_grid_bwd_workspace_bytes.restype = c_i64
+    L.sg_web_score_grid_fwd_bwd.argtypes = [pm, vp, c_i64, vp, c_i64, c_i64, c_i64, vp, vp, c_i64,
+                                            c_i64, vp, c_i32, vp, c_i64, vp, c_i64, vp, c_i64, vp,
+                                            vp, vp, vp]
+    L.sg_web_score_grid_fwd_bwd.restype = c_i32
+    L.sg_web_embed_bwd_workspace_bytes.argtypes = [pm, c_i64]
+    L.sg_web_embed_bwd_workspace_bytes.restype = c_i64
+    L.sg_web_embed_bwd.argtypes = [pm, pc, vp, c_i64, vp, vp, c_i64, vp, vp, vp, vp]
+    L.sg_web_embed_bwd.restype = c_i32
     _lib = L
     return L
 
@@ -285,6 +296,11 @@ WEB_EMBED_SYMBOLS = ('sg_web_embed_dim', 'sg_web_embed_ld', 'sg_web_embed_worksp
 # the symbols of include/siamese_web_search.h (embed-once search for graph-store models: the
 # large-D score grid + top-k in one call, no m x n matrix; detected by presence)
 WEB_SEARCH_SYMBOLS = ('sg_web_search_topk_workspace_bytes', 'sg_web_search_topk')
+
+# the symbols of include/siamese_web_embed_train.h (embed-once training for graph-store
+# models: the large-D grid adjoint and the CSR node-stack backward; detected by presence)
+WEB_EMBED_TRAIN_SYMBOLS = ('sg_web_score_grid_bwd_workspace_bytes', 'sg_web_score_grid_fwd_bwd',
+                           'sg_web_embed_bwd_workspace_bytes', 'sg_web_embed_bwd')
 
 # class_start entries of sg_pair_order_cls (include/siamese_hip.h SG_FAST_CLASSES_P1)
 FAST_CLASSES_P1 = 5
@@ -718,6 +734,45 @@ def web_score_grid(m: SgModel, emb_q, ld_q, emb_db, ld_db, n_q, n_db, params, ap
                                   int(ld_db), int(n_q), int(n_db), _ptr(params),
                                   int(bool(apply_final)), _ptr(out), int(ld_out),
                                   _ptr(workspace), _stream(stream)), 'sg_web_score_grid')
+
+
+_NO_WEB_TRAIN = ('embed-once training of graph-store models serves models on the graph-store '
+                 'path without effective dropout')
+
+
+def web_score_grid_bwd_workspace_bytes(m: SgModel, n_q: int, n_db: int) -> int:
+    b = int(lib().sg_web_score_grid_bwd_workspace_bytes(ctypes.byref(m), int(n_q), int(n_db)))
+    if b < 0:
+        raise SiameseHipError('sg_web_score_grid_bwd_workspace_bytes: ' + _NO_WEB_TRAIN)
+    return b
+
+
+def web_score_grid_fwd_bwd(m: SgModel, emb_q, ld_q, emb_db, ld_db, n_q, n_db, params, labels,
+                           ld_labels, batch_total, y_stats, add_label_term, s_out, ld_s, g_emb_q,
+                           ld_gq, g_emb_db, ld_gdb, grad_out, loss_out, workspace, stream=None):
+    check(lib().sg_web_score_grid_fwd_bwd(
+        ctypes.byref(m), _ptr(emb_q), int(ld_q), _ptr(emb_db), int(ld_db), int(n_q), int(n_db),
+        _ptr(params), _ptr(labels), int(ld_labels), int(batch_total), _ptr(y_stats),
+        int(bool(add_label_term)), _ptr(s_out), int(ld_s), _ptr(g_emb_q), int(ld_gq),
+        _ptr(g_emb_db), int(ld_gdb), _ptr(grad_out), _ptr(loss_out), _ptr(workspace),
+        _stream(stream)), 'sg_web_score_grid_fwd_bwd')
+
+
+def web_embed_bwd_workspace_bytes(m: SgModel, count: int) -> int:
+    b = int(lib().sg_web_embed_bwd_workspace_bytes(ctypes.byref(m), int(count)))
+    if b < 0:
+        raise SiameseHipError('sg_web_embed_bwd_workspace_bytes: ' + _NO_WEB_TRAIN)
+    return b
+
+
+def web_embed_bwd(m: SgModel, store: SgCsrStore, graph_idx, count, params, g_emb, ld_g, grad_out,
+                  workspace, status=None, stream=None):
+    """sg_web_embed_bwd over a CSR store struct: the node layers' range of grad_out from the
+    embedding gradients g_emb [count] rows of stride ld_g."""
+    check(lib().sg_web_embed_bwd(ctypes.byref(m), ctypes.byref(store), _ptr(graph_idx),
+                                 int(count), _ptr(params), _ptr(g_emb), int(ld_g), _ptr(grad_out),
+                                 _ptr(status), _ptr(workspace), _stream(stream)),
+          'sg_web_embed_bwd')
 
 
 def web_search_workspace_bytes(m: SgModel, n_q: int, n_db: int, k: int, seg_cols: int = 0) -> int:

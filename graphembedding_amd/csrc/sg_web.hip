@@ -34,7 +34,7 @@
 #include <mutex>
 #include <vector>
 
-#include "../../include/siamese_web_embed.h"
+#include "../../include/siamese_web_embed_train.h"
 #include "sg_mfma.h"
 #include "sg_paths.h"
 
@@ -2169,7 +2169,106 @@ WebEmbWs web_emb_ws(int64_t count) {
 
 constexpr int64_t kWebEmbMax = (int64_t)1 << 29;   // 2 count instances stay below 2^31
 
+// ---- embed-once training (include/siamese_web_embed_train.h) ----
+constexpr int kWebBwdRows = 512;      // gradient rows of sg_web_embed_bwd's workspace
+constexpr int64_t kWebBwdChunk = 1024;   // entries per forward + backward pass
+
+// a layer whose dropout the path reads would drop (thresholds not "keep all")
+bool web_plan_drops(const WebPlan &W) {
+  const uint32_t all = sg_keep_threshold(1.f);
+  return W.thr0 != all || W.thr1 != all || W.thr2 != all || W.thr4 != all;
+}
+
+// chunk entry x -> graph c0 + x (graph_idx == NULL past the first chunk)
+__global__ void __launch_bounds__(256) web_embed_iota_kernel(int32_t *__restrict__ ids, int64_t cn,
+                                                             int64_t c0) {
+  const int64_t x = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (x < cn) ids[x] = (int32_t)(c0 + x);
+}
+
+// workspace of sg_web_embed_bwd (4-byte words; the header gives the formula)
+struct WebEmbBwdWs {
+  int64_t cc;   // entries per chunk
+  int64_t SLAB, X, GX, MASK, D2, IDS, EMB, total;
+};
+
+WebEmbBwdWs web_emb_bwd_ws(const WebPlan &W, int64_t count) {
+  WebEmbBwdWs w;
+  w.cc = count < kWebBwdChunk ? (count > 0 ? count : 1) : kWebBwdChunk;
+  const int64_t Dp = W.Dp;
+  int64_t o = 0;
+  auto take = [&](int64_t n) { const int64_t r = o; o += (n + 63) & ~(int64_t)63; return r; };
+  w.SLAB = take((int64_t)kWebBwdRows * W.n_gcn);
+  w.X = take(w.cc * Dp);
+  w.GX = take(w.cc * Dp);
+  w.MASK = take(w.cc * Dp * 4);    // uint16 [2 cc][Dp][4]
+  w.D2 = take(w.cc * Dp * 32);     // [2 cc][Dp][16]
+  w.IDS = take(w.cc);
+  w.EMB = o;
+  o += web_emb_ws(w.cc).total + 64;   // sg_web_embed_workspace_bytes(model, cc) / 4
+  w.total = o;
+  return w;
+}
+
+bool web_embed_store_ok(const WebPlan &W, const sg_model_t *model, const sg_csr_store_t *store) {
+  return store && store->node_off && store->types && store->row_ptr && store->col && store->val &&
+         store->n_graphs >= 0 && store->n_max >= 1 && store->n_max <= W.D &&
+         store->n_max <= model->n_max && store->max_nnz >= 0;
+}
+
 }  // namespace
+
+// The instance records and size-class units of `count` entries (workspace `base`,
+// web_emb_ws(count)) and the forward instance kernel over them: entry c runs as the side-0
+// instance q = 2 c and writes row c of X [count][Dp]; with masks / d2 non-null the kernel
+// also stores its keep bits and D2 rows (the backward reads them).  *Gout: the arguments of
+// the launch, for the backward launch over the same units.
+static int web_embed_forward(const WebPlan &W, const sg_csr_store_t *store, const int32_t *graph_idx,
+                             int64_t count, const float *params, float *X, uint16_t *masks,
+                             float *d2, int32_t *status_out, int32_t *base, hipStream_t st,
+                             GcnArgs *Gout) {
+  const WebEmbWs ws = web_emb_ws(count);
+  int4 *inst = (int4 *)(base + ws.INST), *instc = (int4 *)(base + ws.INSTC);
+  int32_t *isort = base + ws.ISORT, *icnt = base + ws.ICNT, *icls = base + ws.ICLS;
+  const unsigned nb256 = (unsigned)((count + 255) / 256);
+  hipLaunchKernelGGL(web_embed_inst_kernel, dim3(nb256), dim3(256), 0, st, graph_idx, count,
+                     store->n_graphs, store->n_max, store->node_off, store->row_ptr, inst, instc,
+                     status_out);
+  // the size-class units of the pair path over the entries (one partition: no id is read)
+  const int n16 = (store->n_max + 15) & ~15;
+  const int cap4 = (n16 / 4) & ~15, cap2 = (n16 / 2) & ~15;
+  hipLaunchKernelGGL(web_icls_count, dim3(ws.nbu), dim3(256), 0, st, (const int4 *)instc,
+                     (const int32_t *)nullptr, count, cap4, cap2, 1, ws.nbu, icnt);
+  hipLaunchKernelGGL(web_icls_scan, dim3(1), dim3(kScanT), 0, st, icnt, ws.nbu, count, 1, icls);
+  hipLaunchKernelGGL(web_icls_scatter, dim3(ws.nbu), dim3(256), 0, st, (const int4 *)instc,
+                     (const int32_t *)nullptr, count, cap4, cap2, 1, ws.nbu,
+                     (const int32_t *)icnt, isort);
+  hipLaunchKernelGGL(web_embed_side0_kernel, dim3(nb256), dim3(256), 0, st, isort, count);
+  GcnArgs &G = *Gout;
+  memset(&G, 0, sizeof(G));
+  G.node_off = store->node_off;
+  G.types = store->types;
+  G.row_ptr = store->row_ptr;
+  G.col = store->col;
+  G.val = store->val;
+  G.inst = inst;
+  G.isorted = isort;
+  G.icls = icls;
+  G.n_pairs = count;
+  G.Cp = count;
+  G.params = params;
+  G.X = X;
+  G.masks = masks;
+  G.d2 = d2;
+  const uint32_t keep_all = sg_keep_threshold(1.f);
+  G.thr0 = G.thr1 = G.thr2 = G.thr4 = keep_all;
+  G.ik0 = G.ik1 = G.ik2 = G.ik4 = 1.f;
+  G.padv = W.padv;
+  G.d_in = W.d_in; G.D = W.D; G.Dp = W.Dp; G.n_gcn = W.n_gcn; G.n_max = store->n_max;
+  G.max_nnz = store->max_nnz;
+  G.ob0 = W.ob0; G.oW1 = W.oW1; G.ob1 = W.ob1; G.oWd = W.oWd; G.obd = W.obd;
+  return gcn_launch(false, W, G, 2 * count, st);
+}
 
 extern "C" {
 
@@ -2196,57 +2295,92 @@ int32_t sg_web_embed(const sg_model_t *model, const sg_csr_store_t *store,
   int rc = web_plan(model, &W);
   if (rc != SG_OK) return rc;
   if (!sg_web_lds_ok(model)) return SG_ERR_UNSUPPORTED;
-  if (!store || !store->node_off || !store->types || !store->row_ptr || !store->col ||
-      !store->val || store->n_graphs < 0 || store->n_max < 1 || store->n_max > W.D ||
-      store->n_max > model->n_max || store->max_nnz < 0)
-    return SG_ERR_ARG;
+  if (!web_embed_store_ok(W, model, store)) return SG_ERR_ARG;
   if (count > kWebEmbMax) return SG_ERR_UNSUPPORTED;
   if (count == 0) return SG_OK;
   if (!params || !emb_out || !workspace) return SG_ERR_ARG;
   hipStream_t st = (hipStream_t)stream;
   (void)hipGetLastError();   // report only this call's launch errors
-  const WebEmbWs ws = web_emb_ws(count);
-  int32_t *base = (int32_t *)workspace;
-  int4 *inst = (int4 *)(base + ws.INST), *instc = (int4 *)(base + ws.INSTC);
-  int32_t *isort = base + ws.ISORT, *icnt = base + ws.ICNT, *icls = base + ws.ICLS;
-  const unsigned nb256 = (unsigned)((count + 255) / 256);
-  hipLaunchKernelGGL(web_embed_inst_kernel, dim3(nb256), dim3(256), 0, st, graph_idx, count,
-                     store->n_graphs, store->n_max, store->node_off, store->row_ptr, inst, instc,
-                     status_out);
-  // the size-class units of the pair path over the entries (one partition: no id is read)
-  const int n16 = (store->n_max + 15) & ~15;
-  const int cap4 = (n16 / 4) & ~15, cap2 = (n16 / 2) & ~15;
-  hipLaunchKernelGGL(web_icls_count, dim3(ws.nbu), dim3(256), 0, st, (const int4 *)instc,
-                     (const int32_t *)nullptr, count, cap4, cap2, 1, ws.nbu, icnt);
-  hipLaunchKernelGGL(web_icls_scan, dim3(1), dim3(kScanT), 0, st, icnt, ws.nbu, count, 1, icls);
-  hipLaunchKernelGGL(web_icls_scatter, dim3(ws.nbu), dim3(256), 0, st, (const int4 *)instc,
-                     (const int32_t *)nullptr, count, cap4, cap2, 1, ws.nbu,
-                     (const int32_t *)icnt, isort);
-  hipLaunchKernelGGL(web_embed_side0_kernel, dim3(nb256), dim3(256), 0, st, isort, count);
   GcnArgs G;
-  memset(&G, 0, sizeof(G));
-  G.node_off = store->node_off;
-  G.types = store->types;
-  G.row_ptr = store->row_ptr;
-  G.col = store->col;
-  G.val = store->val;
-  G.inst = inst;
-  G.isorted = isort;
-  G.icls = icls;
-  G.n_pairs = count;
-  G.Cp = count;
-  G.params = params;
-  G.X = emb_out;
-  const uint32_t keep_all = sg_keep_threshold(1.f);
-  G.thr0 = G.thr1 = G.thr2 = G.thr4 = keep_all;
-  G.ik0 = G.ik1 = G.ik2 = G.ik4 = 1.f;
-  G.padv = W.padv;
-  G.d_in = W.d_in; G.D = W.D; G.Dp = W.Dp; G.n_gcn = W.n_gcn; G.n_max = store->n_max;
-  G.max_nnz = store->max_nnz;
-  G.ob0 = W.ob0; G.oW1 = W.oW1; G.ob1 = W.ob1; G.oWd = W.oWd; G.obd = W.obd;
-  if ((rc = gcn_launch(false, W, G, 2 * count, st)) != SG_OK) return rc;
+  if ((rc = web_embed_forward(W, store, graph_idx, count, params, emb_out, nullptr, nullptr,
+                              status_out, (int32_t *)workspace, st, &G)) != SG_OK)
+    return rc;
   hipLaunchKernelGGL(web_embed_zero_kernel, dim3((unsigned)((count + 3) / 4)), dim3(256), 0, st,
-                     (const int4 *)inst, count, W.Dp, emb_out);
+                     G.inst, count, W.Dp, emb_out);
+  return web_status();
+}
+
+// Embed-once training for path-3 models (include/siamese_web_embed_train.h): the backward of
+// the node stack of single graphs through both instance kernels, unchanged.  Per chunk of
+// kWebBwdChunk entries: web_embed_forward with the keep bits (all set) and D2 rows stored,
+// then the backward instance kernel over the same units with GX = the entries' rows of
+// g_emb; it adds into one slab row per workgroup, chunk after chunk in stream order, and one
+// fixed-order column sum follows.
+int64_t sg_web_embed_bwd_workspace_bytes(const sg_model_t *model, int64_t count) {
+  WebPlan W;
+  if (count < 0 || count > kWebEmbMax || web_plan(model, &W) != SG_OK || !sg_web_lds_ok(model) ||
+      web_plan_drops(W))
+    return -1;
+  return web_emb_bwd_ws(W, count).total * 4 + 256;
+}
+
+int32_t sg_web_embed_bwd(const sg_model_t *model, const sg_csr_store_t *store,
+                         const int32_t *graph_idx, int64_t count, const float *params,
+                         const float *g_emb, int64_t ld_g, float *grad_out,
+                         int32_t *status_out, void *workspace, sg_stream_t stream) {
+  if (!model || count < 0) return SG_ERR_ARG;
+  WebPlan W;
+  int rc = web_plan(model, &W);
+  if (rc != SG_OK) return rc;
+  if (!sg_web_lds_ok(model)) return SG_ERR_UNSUPPORTED;
+  if (web_plan_drops(W)) return SG_ERR_UNSUPPORTED;
+  if (!web_embed_store_ok(W, model, store)) return SG_ERR_ARG;
+  if (count > kWebEmbMax) return SG_ERR_UNSUPPORTED;
+  if (!grad_out) return SG_ERR_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  if (count == 0) {
+    (void)hipGetLastError();
+    if (hipMemsetAsync(grad_out, 0, (size_t)W.n_gcn * 4u, st) != hipSuccess) return SG_ERR_HIP;
+    return web_status();
+  }
+  if (!params || !g_emb || !workspace || ld_g < W.D) return SG_ERR_ARG;
+  // one gradient row per workgroup of the backward instance kernel (gcn_launch: one per CU)
+  const int rows = sg_num_cus();
+  if (rows < 1 || rows > kWebBwdRows) return SG_ERR_UNSUPPORTED;
+  (void)hipGetLastError();   // report only this call's launch errors
+  const WebEmbBwdWs ws = web_emb_bwd_ws(W, count);
+  float *base = (float *)(((uintptr_t)workspace + 15u) & ~(uintptr_t)15u);   // 16-byte D2 rows
+  float *slab = base + ws.SLAB, *X = base + ws.X, *GXc = base + ws.GX, *D2 = base + ws.D2;
+  uint16_t *MASK = (uint16_t *)(base + ws.MASK);
+  int32_t *ids = (int32_t *)(base + ws.IDS), *emb = (int32_t *)(base + ws.EMB);
+  if (hipMemsetAsync(slab, 0, (size_t)rows * W.n_gcn * 4u, st) != hipSuccess) return SG_ERR_HIP;
+  const int Dp = W.Dp;
+  for (int64_t c0 = 0; c0 < count; c0 += ws.cc) {
+    const int64_t cn = count - c0 < ws.cc ? count - c0 : ws.cc;
+    const int32_t *gidx = graph_idx ? graph_idx + c0 : ids;
+    if (!graph_idx)
+      hipLaunchKernelGGL(web_embed_iota_kernel, dim3((unsigned)((cn + 255) / 256)), dim3(256), 0,
+                         st, ids, cn, c0);
+    // forward with the keep bits and D2 rows stored (X: the chunk's embeddings, not used)
+    GcnArgs G;
+    if ((rc = web_embed_forward(W, store, gidx, cn, params, X, MASK, D2, status_out, emb, st,
+                                &G)) != SG_OK)
+      return rc;
+    // ∂L/∂x of entry c at row c of a [cn][Dp] array: g_emb itself when its stride is Dp
+    const float *GX = g_emb + c0 * ld_g;
+    if (ld_g != Dp) {
+      if (hipMemcpy2DAsync(GXc, (size_t)Dp * 4u, GX, (size_t)ld_g * 4u, (size_t)W.D * 4u,
+                           (size_t)cn, hipMemcpyDeviceToDevice, st) != hipSuccess)
+        return SG_ERR_HIP;
+      GX = GXc;
+    }
+    G.GX = GX;
+    G.slab = slab;
+    if ((rc = gcn_launch(true, W, G, 2 * cn, st)) != SG_OK) return rc;
+  }
+  hipLaunchKernelGGL(web_colsum, dim3((W.n_gcn + 63) / 64), dim3(1024), 0, st,
+                     (const float *)slab, rows, W.n_gcn, W.n_gcn, grad_out, 1,
+                     (const float *)nullptr, -1);
   return web_status();
 }
 

@@ -167,7 +167,8 @@ void web_dispatch_nsmax(int ns, F &&f) {
 // accumulate in two independent chains (the instruction issues in 32 cycles with 40 of
 // dependent latency), summed at the end.  Epilogue as sg_grid_kernel: relu, column weights
 // and the k < K mask, the 16-lane row sum; lanes c < 4 of group g then hold the scores of
-// rows 4 g + c of the tile.
+// rows 4 g + c of the tile.  web_score is web_mk (the k-steps) followed by web_score_mk (the
+// epilogue); the training grid (sg_web_train.hip) calls the two halves and keeps the m_k.
 // ---------------------------------------------------------------------------
 template <int NSMAX>
 __device__ __forceinline__ void web_load_a(const float *edb, int64_t ld_db, int64_t n, int D,
@@ -212,11 +213,11 @@ __device__ __forceinline__ void web_q_store(float *dst, int tid, int nf4,
   }
 }
 
+// the k-steps: m_k of the tile against the staged table, register r = row 4 g + r of the tile,
+// column k = c
 template <int NSMAX>
-__device__ __forceinline__ float web_score(const float (&a)[NSMAX], const float *cur, int ns,
-                                           int lane, int c, bool kmask, float wk, float usum,
-                                           int act, int apply_final, int final_act,
-                                           float yeta) {
+__device__ __forceinline__ void web_mk(const float (&a)[NSMAX], const float *cur, int ns,
+                                       int lane, float (&x)[4]) {
   f4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
   for (int s = 0; s < NSMAX; ++s) {   // (no break: the loop must unroll, a[] stays in registers)
@@ -226,12 +227,17 @@ __device__ __forceinline__ float web_score(const float (&a)[NSMAX], const float 
       else acc0 = mfma4(a[s], b, acc0);
     }
   }
+#pragma unroll
+  for (int r = 0; r < 4; ++r) x[r] = acc0[r] + acc1[r];
+}
+
+// the epilogue: the score of row 4 g + c from the m_k of web_mk, in lanes c < 4
+__device__ __forceinline__ float web_score_mk(const float (&x)[4], int c, bool kmask, float wk,
+                                              float usum, int act, int apply_final,
+                                              int final_act, float yeta) {
   float v[4];
 #pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const float x = acc0[r] + acc1[r];
-    v[r] = kmask ? sg_act(act, x) * wk : 0.f;
-  }
+  for (int r = 0; r < 4; ++r) v[r] = kmask ? sg_act(act, x[r]) * wk : 0.f;
 #pragma unroll
   for (int r = 0; r < 4; ++r) v[r] = sgk::row_sum16(v[r]);
   float sc = v[0];
@@ -240,6 +246,16 @@ __device__ __forceinline__ float web_score(const float (&a)[NSMAX], const float 
   sc *= usum;
   if (apply_final) sc = sg_final(final_act, yeta, sc);
   return sc;
+}
+
+template <int NSMAX>
+__device__ __forceinline__ float web_score(const float (&a)[NSMAX], const float *cur, int ns,
+                                           int lane, int c, bool kmask, float wk, float usum,
+                                           int act, int apply_final, int final_act,
+                                           float yeta) {
+  float x[4];
+  web_mk<NSMAX>(a, cur, ns, lane, x);
+  return web_score_mk(x, c, kmask, wk, usum, act, apply_final, final_act, yeta);
 }
 
 }  // namespace

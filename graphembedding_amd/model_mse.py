@@ -136,6 +136,9 @@ class GridProblem:
     ws_grid: object
     ws_embed: object
     dropout: Optional[str] = None   # None: dropout 0 only; 'graph': one mask set per graph
+    # graph-store (Web) problems (web_grid_problem): store_dev is (CsrStore, its device
+    # struct), the embedding buffers are [*][ld] (ld = D rounded up to 128)
+    ws_fwd: object = None           # workspace of sg_web_embed
 
     def check(self):
         """Raise if a kernel reported a bad graph id or node count (synchronises)."""
@@ -847,6 +850,103 @@ class SiameseGCNTNMSE(object):
         return: loss_mse + weight decay at the pre-update parameters).  With dropout='graph'
         every step draws new masks (the seed follows step_count)."""
         self.grid_fwd_bwd(store, labels, q_idx, db_idx, dropout=dropout)
+        if self.grad_hook is not None:
+            self.grad_hook(self)
+        self.apply_adam()
+        self.step_count += 1
+        if not sync:
+            return None
+        return float(self.loss_buf[0].item() + self.reg_buf[0].item())
+
+    # ---- embed-once training for graph-store models
+    # (include/siamese_web_embed_train.h: dropout 0 only) ----
+    def web_grid_problem(self, store, labels, q_idx=None, db_idx=None, y_stats=None):
+        """grid_problem for a graph-store (Web) model: the device-resident state of an m x n
+        block of pairs over a web.CsrStore (query q_idx[i] as graph 1, database db_idx[j] as
+        graph 2; None = every store graph) with labels [m][n].  The embedding buffers keep
+        the [*][ld] rows of sg_web_embed (ld = D rounded up to 128).  Build once, step many
+        times (web_grid_fwd_bwd / web_grid_train_step).  Needs flags.dropout = 0."""
+        torch = self.torch
+        self._only_web('web_grid_problem')
+        self._no_dropout('web_grid_problem')
+        self.check_node_counts(store.n, 'web_grid_problem')
+        G = len(store)
+        if G == 0 or int(np.asarray(store.n).min()) < 1:
+            raise _lib.SiameseHipError('web_grid_problem: every store graph needs at least one '
+                                       'node')
+        q = np.arange(G) if q_idx is None else np.asarray(q_idx, np.int64).reshape(-1)
+        db = np.arange(G) if db_idx is None else np.asarray(db_idx, np.int64).reshape(-1)
+        both = np.concatenate([q, db])
+        if both.size and (both.min() < 0 or both.max() >= G):
+            raise _lib.SiameseHipError('web_grid_problem: graph ids must lie in [0, {})'.format(G))
+        uniq, inv = np.unique(both, return_inverse=True)
+        m, n, dev = int(q.size), int(db.size), self.device
+        lab = torch.as_tensor(labels if torch.is_tensor(labels) else
+                              np.asarray(labels, np.float32), dtype=torch.float32,
+                              device=dev).contiguous()
+        if tuple(lab.shape) != (m, n):
+            raise _lib.SiameseHipError('web_grid_problem: labels must be [{}][{}]'.format(m, n))
+        if y_stats is None:
+            y_stats = _label_stats(torch, lab, m * n)
+        ld, U = _lib.web_embed_ld(self.sg), int(uniq.size)
+        f32 = dict(dtype=torch.float32, device=dev)
+
+        def ws(nbytes):
+            return torch.empty(nbytes // 4 + 1, **f32)
+        # the gradient buffers start as zeros: the kernels leave columns [D, ld) untouched
+        return GridProblem(
+            store_dev=(store, store.to_device(dev)), m=m, n=n, labels=lab, y_stats=y_stats,
+            uniq=torch.from_numpy(uniq.astype(np.int32)).to(dev),
+            q_pos=torch.from_numpy(inv[:m].astype(np.int64)).to(dev),
+            db_pos=torch.from_numpy(inv[m:].astype(np.int64)).to(dev),
+            identity=bool(m == n == U and np.array_equal(q, uniq) and np.array_equal(db, uniq)),
+            emb=torch.empty((U, ld), **f32), g_emb=torch.zeros((U, ld), **f32),
+            g_q=torch.zeros((m, ld), **f32), g_db=torch.zeros((n, ld), **f32),
+            status=torch.zeros(1, dtype=torch.int32, device=dev),
+            ws_grid=ws(_lib.web_score_grid_bwd_workspace_bytes(self.sg, m, n)),
+            ws_embed=ws(_lib.web_embed_bwd_workspace_bytes(self.sg, U)),
+            ws_fwd=ws(_lib.web_embed_workspace_bytes(self.sg, U)))
+
+    def web_grid_fwd_bwd(self, store, labels=None, q_idx=None, db_idx=None, add_label_term=True,
+                         s_out=None):
+        """grid_fwd_bwd for a graph-store (Web) model: every distinct graph's CSR node stack
+        runs forward once (sg_web_embed), the large-D NTN grid runs forward and backward
+        (sg_web_score_grid_fwd_bwd), the query-role and database-role gradients of each graph
+        are summed and go once through its node stack (sg_web_embed_bwd).  Leaves
+        Σ∂loss_mse/∂θ in self.grad and loss_mse in self.loss_buf[0] where fwd_bwd over the
+        m·n pairs (web_batch, batch_total = m·n) leaves them, up to fp32 summation order.
+        store: a web.CsrStore with labels [m][n], or a web_grid_problem(...) built once.
+        s_out: [m][n] pre-activation scores, optional.  Needs flags.dropout = 0."""
+        self._only_web('web_grid_fwd_bwd')
+        self._no_dropout('web_grid_fwd_bwd')
+        gp = store if isinstance(store, GridProblem) else self.web_grid_problem(
+            store, labels, q_idx, db_idx)
+        if gp.ws_fwd is None:
+            raise _lib.SiameseHipError('web_grid_fwd_bwd: the problem was built by grid_problem; '
+                                       'use web_grid_problem')
+        sg, csr = self.sg, gp.store_dev[1]
+        U, ld = int(gp.uniq.numel()), int(gp.emb.shape[1])
+        _lib.web_embed(sg, csr, gp.uniq, U, self.params, gp.emb, gp.ws_fwd, gp.status)
+        eq, edb = (gp.emb, gp.emb) if gp.identity else (gp.emb[gp.q_pos], gp.emb[gp.db_pos])
+        _lib.web_score_grid_fwd_bwd(sg, eq, ld, edb, ld, gp.m, gp.n, self.params, gp.labels,
+                                    gp.n, gp.m * gp.n, gp.y_stats, add_label_term, s_out, gp.n,
+                                    gp.g_q, ld, gp.g_db, ld, self.grad, self.loss_buf,
+                                    gp.ws_grid)
+        if gp.identity:
+            self.torch.add(gp.g_q, gp.g_db, out=gp.g_emb)
+        else:
+            gp.g_emb.zero_()
+            gp.g_emb.index_add_(0, gp.q_pos, gp.g_q)
+            gp.g_emb.index_add_(0, gp.db_pos, gp.g_db)
+        _lib.web_embed_bwd(sg, csr, gp.uniq, U, self.params, gp.g_emb, ld, self.grad,
+                           gp.ws_embed, gp.status)
+        return gp
+
+    def web_grid_train_step(self, store, labels=None, q_idx=None, db_idx=None, sync=True):
+        """web_grid_fwd_bwd followed by Adam: train_step's embed-once counterpart for
+        graph-store models (same loss return: loss_mse + weight decay at the pre-update
+        parameters)."""
+        self.web_grid_fwd_bwd(store, labels, q_idx, db_idx)
         if self.grad_hook is not None:
             self.grad_hook(self)
         self.apply_adam()
