@@ -251,6 +251,18 @@ def lib():
     L.sg_web_embed_bwd_workspace_bytes.restype = c_i64
     L.sg_web_embed_bwd.argtypes = [pm, pc, vp, c_i64, vp, vp, c_i64, vp, vp, vp, vp]
     L.sg_web_embed_bwd.restype = c_i32
+    # embed-once training of graph-store models with graph-keyed dropout
+    # (include/siamese_web_embed_drop.h); a library without them still loads
+    if all(hasattr(L, s) for s in WEB_EMBED_DROP_SYMBOLS):
+        L.sg_web_embed_drop_workspace_bytes.argtypes = [pm, c_i64]
+        L.sg_web_embed_drop_workspace_bytes.restype = c_i64
+        L.sg_web_embed_drop.argtypes = [pm, pc, vp, c_i64, c_i64, vp, c_u64, vp, vp, vp, vp]
+        L.sg_web_embed_drop.restype = c_i32
+        L.sg_web_embed_drop_bwd_workspace_bytes.argtypes = [pm, c_i64]
+        L.sg_web_embed_drop_bwd_workspace_bytes.restype = c_i64
+        L.sg_web_embed_drop_bwd.argtypes = [pm, pc, vp, c_i64, c_i64, vp, c_u64, vp, c_i64, vp,
+                                            vp, vp, vp]
+        L.sg_web_embed_drop_bwd.restype = c_i32
     _lib = L
     return L
 
@@ -301,6 +313,11 @@ WEB_SEARCH_SYMBOLS = ('sg_web_search_topk_workspace_bytes', 'sg_web_search_topk'
 # models: the large-D grid adjoint and the CSR node-stack backward; detected by presence)
 WEB_EMBED_TRAIN_SYMBOLS = ('sg_web_score_grid_bwd_workspace_bytes', 'sg_web_score_grid_fwd_bwd',
                            'sg_web_embed_bwd_workspace_bytes', 'sg_web_embed_bwd')
+
+# the symbols of include/siamese_web_embed_drop.h (embed-once training of graph-store models
+# with graph-keyed dropout masks; detected by presence)
+WEB_EMBED_DROP_SYMBOLS = ('sg_web_embed_drop_workspace_bytes', 'sg_web_embed_drop',
+                          'sg_web_embed_drop_bwd_workspace_bytes', 'sg_web_embed_drop_bwd')
 
 # class_start entries of sg_pair_order_cls (include/siamese_hip.h SG_FAST_CLASSES_P1)
 FAST_CLASSES_P1 = 5
@@ -773,6 +790,54 @@ def web_embed_bwd(m: SgModel, store: SgCsrStore, graph_idx, count, params, g_emb
                                  int(count), _ptr(params), _ptr(g_emb), int(ld_g), _ptr(grad_out),
                                  _ptr(status), _ptr(workspace), _stream(stream)),
           'sg_web_embed_bwd')
+
+
+_NO_WEB_DROP = ('embed-once training with graph-keyed dropout serves models on the graph-store '
+                'path whose stack fits the LDS')
+
+
+def _web_drop_fn(name: str):
+    fn = getattr(lib(), name, None)
+    if fn is None or fn.argtypes is None:
+        raise SiameseHipError(name + ': this libsiamese_hip.so has no '
+                              'include/siamese_web_embed_drop.h entry points')
+    return fn
+
+
+def web_embed_drop_workspace_bytes(m: SgModel, count: int) -> int:
+    b = int(_web_drop_fn('sg_web_embed_drop_workspace_bytes')(ctypes.byref(m), int(count)))
+    if b < 0:
+        raise SiameseHipError('sg_web_embed_drop_workspace_bytes: ' + _NO_WEB_DROP)
+    return b
+
+
+def web_embed_drop(m: SgModel, store: SgCsrStore, graph_idx, count, entry_offset, params, seed,
+                   emb_out, workspace, status=None, stream=None):
+    """sg_web_embed_drop: sg_web_embed with graph-keyed dropout masks (entry c is side
+    (entry_offset + c) & 1 of unit (entry_offset + c) >> 1 under `seed`); emb_out
+    [count][web_embed_ld] receives the embeddings through the head's input mask."""
+    check(_web_drop_fn('sg_web_embed_drop')(
+        ctypes.byref(m), ctypes.byref(store), _ptr(graph_idx), int(count), int(entry_offset),
+        _ptr(params), int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(emb_out), _ptr(status),
+        _ptr(workspace), _stream(stream)), 'sg_web_embed_drop')
+
+
+def web_embed_drop_bwd_workspace_bytes(m: SgModel, count: int) -> int:
+    b = int(_web_drop_fn('sg_web_embed_drop_bwd_workspace_bytes')(ctypes.byref(m), int(count)))
+    if b < 0:
+        raise SiameseHipError('sg_web_embed_drop_bwd_workspace_bytes: ' + _NO_WEB_DROP)
+    return b
+
+
+def web_embed_drop_bwd(m: SgModel, store: SgCsrStore, graph_idx, count, entry_offset, params,
+                       seed, g_emb, ld_g, grad_out, workspace, status=None, stream=None):
+    """sg_web_embed_drop_bwd: the node layers' range of grad_out from g_emb [count] rows of
+    stride ld_g, the gradients of the masked embeddings web_embed_drop returned for the same
+    entries, entry_offset and seed."""
+    check(_web_drop_fn('sg_web_embed_drop_bwd')(
+        ctypes.byref(m), ctypes.byref(store), _ptr(graph_idx), int(count), int(entry_offset),
+        _ptr(params), int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(g_emb), int(ld_g), _ptr(grad_out),
+        _ptr(status), _ptr(workspace), _stream(stream)), 'sg_web_embed_drop_bwd')
 
 
 def web_search_workspace_bytes(m: SgModel, n_q: int, n_db: int, k: int, seg_cols: int = 0) -> int:

@@ -46,6 +46,7 @@ def _stale() -> bool:
     deps.append(os.path.join(os.path.dirname(_HERE), 'include', 'siamese_web_embed.h'))
     deps.append(os.path.join(os.path.dirname(_HERE), 'include', 'siamese_web_search.h'))
     deps.append(os.path.join(os.path.dirname(_HERE), 'include', 'siamese_web_embed_train.h'))
+    deps.append(os.path.join(os.path.dirname(_HERE), 'include', 'siamese_web_embed_drop.h'))
     deps.append(os.path.abspath(__file__))
     return any(os.path.isfile(d) and os.path.getmtime(d) > t for d in deps)
 

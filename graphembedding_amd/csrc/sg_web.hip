@@ -34,7 +34,7 @@
 #include <mutex>
 #include <vector>
 
-#include "../../include/siamese_web_embed_train.h"
+#include "../../include/siamese_web_embed_drop.h"
 #include "sg_mfma.h"
 #include "sg_paths.h"
 
@@ -2192,15 +2192,16 @@ struct WebEmbBwdWs {
   int64_t SLAB, X, GX, MASK, D2, IDS, EMB, total;
 };
 
-WebEmbBwdWs web_emb_bwd_ws(const WebPlan &W, int64_t count) {
+// (drop: sg_web_embed_drop_bwd, whose X and GX hold both sides of (cc + 1) / 2 units)
+WebEmbBwdWs web_emb_bwd_ws(const WebPlan &W, int64_t count, bool drop = false) {
   WebEmbBwdWs w;
   w.cc = count < kWebBwdChunk ? (count > 0 ? count : 1) : kWebBwdChunk;
-  const int64_t Dp = W.Dp;
+  const int64_t Dp = W.Dp, xr = drop ? (w.cc + 1) / 2 * 2 : w.cc;
   int64_t o = 0;
   auto take = [&](int64_t n) { const int64_t r = o; o += (n + 63) & ~(int64_t)63; return r; };
   w.SLAB = take((int64_t)kWebBwdRows * W.n_gcn);
-  w.X = take(w.cc * Dp);
-  w.GX = take(w.cc * Dp);
+  w.X = take(xr * Dp);
+  w.GX = take(xr * Dp);
   w.MASK = take(w.cc * Dp * 4);    // uint16 [2 cc][Dp][4]
   w.D2 = take(w.cc * Dp * 32);     // [2 cc][Dp][16]
   w.IDS = take(w.cc);
@@ -2216,6 +2217,53 @@ bool web_embed_store_ok(const WebPlan &W, const sg_model_t *model, const sg_csr_
          store->n_max <= model->n_max && store->max_nnz >= 0;
 }
 
+// ---- embed-once training with graph-keyed dropout (include/siamese_web_embed_drop.h) ----
+// The instance kernels keep side s of unit u at row s Cp + u of X and GX; the caller's rows
+// are entry-major.  Entry c of a chunk of cn entries (Cp = (cn + 1) / 2) <-> that row:
+__host__ __device__ inline int64_t web_drop_row(int64_t c, int64_t Cp) {
+  return (c & 1) * Cp + (c >> 1);
+}
+
+// emb[c] = the entry's row of the side-major Xs, or zeros for the empty record (one
+// wavefront per row)
+__global__ void __launch_bounds__(256) web_drop_rows_out_kernel(const float *__restrict__ Xs,
+                                                                const int4 *__restrict__ inst,
+                                                                int64_t cn, int64_t Cp, int Dp,
+                                                                float *__restrict__ emb) {
+  const int64_t c = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (c >= cn) return;
+  const bool ok = inst[c].y != 0;
+  const float *src = Xs + web_drop_row(c, Cp) * Dp;
+  float *dst = emb + c * Dp;
+  for (int a = threadIdx.x & 63; a < Dp; a += SG_WAVE) dst[a] = ok ? src[a] : 0.f;
+}
+
+// GXs[the entry's row][0 .. D) = g[c][0 .. D) (rows of stride ld_g; the instance kernel
+// reads the columns below the entry's node count only)
+__global__ void __launch_bounds__(256) web_drop_rows_in_kernel(const float *__restrict__ g,
+                                                               int64_t ld_g, int64_t cn, int64_t Cp,
+                                                               int D, int Dp,
+                                                               float *__restrict__ GXs) {
+  const int64_t c = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (c >= cn) return;
+  const float *src = g + c * ld_g;
+  float *dst = GXs + web_drop_row(c, Cp) * Dp;
+  for (int a = threadIdx.x & 63; a < D; a += SG_WAVE) dst[a] = src[a];
+}
+
+// workspace of sg_web_embed_drop (4-byte words): the side-major rows, then web_emb_ws
+int64_t web_emb_drop_xs(const WebPlan &W, int64_t count) {
+  const int64_t n = (count + 1) / 2 * 2 * W.Dp;
+  return (n + 63) & ~(int64_t)63;
+}
+
+// the arguments both dropout calls check alike
+int web_drop_args_ok(const sg_model_t *model, int64_t count, int64_t entry_offset) {
+  if (!model || count < 0 || entry_offset < 0 || (entry_offset & 1)) return SG_ERR_ARG;
+  if (!(model->keep_prob > 0.f && model->keep_prob <= 1.f)) return SG_ERR_ARG;
+  return SG_OK;
+}
+
 }  // namespace
 
 // The instance records and size-class units of `count` entries (workspace `base`,
@@ -2223,10 +2271,18 @@ bool web_embed_store_ok(const WebPlan &W, const sg_model_t *model, const sg_csr_
 // instance q = 2 c and writes row c of X [count][Dp]; with masks / d2 non-null the kernel
 // also stores its keep bits and D2 rows (the backward reads them).  *Gout: the arguments of
 // the launch, for the backward launch over the same units.
+// With `drop` (include/siamese_web_embed_drop.h) entry c runs as instance q = c, side c & 1
+// of unit drop->unit0 + (c >> 1), under the model's keep thresholds and drop->key: X is
+// then the kernel's side-major [2][(count + 1) / 2][Dp] (web_drop_row).
+struct WebDrop {
+  uint32_t key;
+  int64_t unit0;
+};
+
 static int web_embed_forward(const WebPlan &W, const sg_csr_store_t *store, const int32_t *graph_idx,
                              int64_t count, const float *params, float *X, uint16_t *masks,
                              float *d2, int32_t *status_out, int32_t *base, hipStream_t st,
-                             GcnArgs *Gout) {
+                             GcnArgs *Gout, const WebDrop *drop = nullptr) {
   const WebEmbWs ws = web_emb_ws(count);
   int4 *inst = (int4 *)(base + ws.INST), *instc = (int4 *)(base + ws.INSTC);
   int32_t *isort = base + ws.ISORT, *icnt = base + ws.ICNT, *icls = base + ws.ICLS;
@@ -2243,7 +2299,8 @@ static int web_embed_forward(const WebPlan &W, const sg_csr_store_t *store, cons
   hipLaunchKernelGGL(web_icls_scatter, dim3(ws.nbu), dim3(256), 0, st, (const int4 *)instc,
                      (const int32_t *)nullptr, count, cap4, cap2, 1, ws.nbu,
                      (const int32_t *)icnt, isort);
-  hipLaunchKernelGGL(web_embed_side0_kernel, dim3(nb256), dim3(256), 0, st, isort, count);
+  // the sorted entries are the instances themselves under dropout (no side to skip)
+  if (!drop) hipLaunchKernelGGL(web_embed_side0_kernel, dim3(nb256), dim3(256), 0, st, isort, count);
   GcnArgs &G = *Gout;
   memset(&G, 0, sizeof(G));
   G.node_off = store->node_off;
@@ -2263,10 +2320,19 @@ static int web_embed_forward(const WebPlan &W, const sg_csr_store_t *store, cons
   const uint32_t keep_all = sg_keep_threshold(1.f);
   G.thr0 = G.thr1 = G.thr2 = G.thr4 = keep_all;
   G.ik0 = G.ik1 = G.ik2 = G.ik4 = 1.f;
+  if (drop) {
+    G.inst = instc;   // one record per entry: instance q = entry q
+    G.n_pairs = G.Cp = (count + 1) / 2;
+    G.key = drop->key;
+    G.pair_offset = drop->unit0;
+    G.thr0 = W.thr0; G.thr1 = W.thr1; G.thr2 = W.thr2; G.thr4 = W.thr4;
+    G.ik0 = W.ik0; G.ik1 = W.ik1; G.ik2 = W.ik2; G.ik4 = W.ik4;
+  }
   G.padv = W.padv;
   G.d_in = W.d_in; G.D = W.D; G.Dp = W.Dp; G.n_gcn = W.n_gcn; G.n_max = store->n_max;
   G.max_nnz = store->max_nnz;
   G.ob0 = W.ob0; G.oW1 = W.oW1; G.ob1 = W.ob1; G.oWd = W.oWd; G.obd = W.obd;
+  // (2 count under dropout too: the launch shape of sg_web_embed, whatever the masks)
   return gcn_launch(false, W, G, 2 * count, st);
 }
 
@@ -2375,6 +2441,107 @@ int32_t sg_web_embed_bwd(const sg_model_t *model, const sg_csr_store_t *store,
       GX = GXc;
     }
     G.GX = GX;
+    G.slab = slab;
+    if ((rc = gcn_launch(true, W, G, 2 * cn, st)) != SG_OK) return rc;
+  }
+  hipLaunchKernelGGL(web_colsum, dim3((W.n_gcn + 63) / 64), dim3(1024), 0, st,
+                     (const float *)slab, rows, W.n_gcn, W.n_gcn, grad_out, 1,
+                     (const float *)nullptr, -1);
+  return web_status();
+}
+
+// Embed-once training with graph-keyed dropout (include/siamese_web_embed_drop.h): the two
+// calls above with entry c' = entry_offset + c scheduled as instance c of its chunk (side
+// c' & 1 of unit c' >> 1: chunks start on even entries) under the model's keep thresholds,
+// so the instance kernels, unchanged, draw and store the pair path's masks.  Their X and GX
+// are side-major: web_drop_rows_out_kernel / web_drop_rows_in_kernel move the caller's rows.
+int64_t sg_web_embed_drop_workspace_bytes(const sg_model_t *model, int64_t count) {
+  WebPlan W;
+  if (count < 0 || count > kWebEmbMax || web_plan(model, &W) != SG_OK || !sg_web_lds_ok(model))
+    return -1;
+  return (web_emb_drop_xs(W, count) + web_emb_ws(count).total) * 4 + 256;
+}
+
+int32_t sg_web_embed_drop(const sg_model_t *model, const sg_csr_store_t *store,
+                          const int32_t *graph_idx, int64_t count, int64_t entry_offset,
+                          const float *params, uint64_t seed, float *emb_out,
+                          int32_t *status_out, void *workspace, sg_stream_t stream) {
+  int rc = web_drop_args_ok(model, count, entry_offset);
+  if (rc != SG_OK) return rc;
+  WebPlan W;
+  if ((rc = web_plan(model, &W)) != SG_OK) return rc;
+  if (!sg_web_lds_ok(model)) return SG_ERR_UNSUPPORTED;
+  if (!web_embed_store_ok(W, model, store)) return SG_ERR_ARG;
+  if (count > kWebEmbMax || entry_offset > kWebEmbMax - count) return SG_ERR_UNSUPPORTED;
+  if (count == 0) return SG_OK;
+  if (!params || !emb_out || !workspace) return SG_ERR_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  (void)hipGetLastError();   // report only this call's launch errors
+  float *Xs = (float *)(((uintptr_t)workspace + 15u) & ~(uintptr_t)15u);
+  int32_t *emb = (int32_t *)(Xs + web_emb_drop_xs(W, count));
+  const WebDrop drop = {sg_seed_key(seed), entry_offset >> 1};
+  GcnArgs G;
+  if ((rc = web_embed_forward(W, store, graph_idx, count, params, Xs, nullptr, nullptr,
+                              status_out, emb, st, &G, &drop)) != SG_OK)
+    return rc;
+  hipLaunchKernelGGL(web_drop_rows_out_kernel, dim3((unsigned)((count + 3) / 4)), dim3(256), 0,
+                     st, (const float *)Xs, G.inst, count, G.Cp, W.Dp, emb_out);
+  return web_status();
+}
+
+int64_t sg_web_embed_drop_bwd_workspace_bytes(const sg_model_t *model, int64_t count) {
+  WebPlan W;
+  if (count < 0 || count > kWebEmbMax || web_plan(model, &W) != SG_OK || !sg_web_lds_ok(model))
+    return -1;
+  return web_emb_bwd_ws(W, count, true).total * 4 + 256;
+}
+
+int32_t sg_web_embed_drop_bwd(const sg_model_t *model, const sg_csr_store_t *store,
+                              const int32_t *graph_idx, int64_t count, int64_t entry_offset,
+                              const float *params, uint64_t seed, const float *g_emb,
+                              int64_t ld_g, float *grad_out, int32_t *status_out,
+                              void *workspace, sg_stream_t stream) {
+  int rc = web_drop_args_ok(model, count, entry_offset);
+  if (rc != SG_OK) return rc;
+  WebPlan W;
+  if ((rc = web_plan(model, &W)) != SG_OK) return rc;
+  if (!sg_web_lds_ok(model)) return SG_ERR_UNSUPPORTED;
+  if (!web_embed_store_ok(W, model, store)) return SG_ERR_ARG;
+  if (count > kWebEmbMax || entry_offset > kWebEmbMax - count) return SG_ERR_UNSUPPORTED;
+  if (!grad_out) return SG_ERR_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  if (count == 0) {
+    (void)hipGetLastError();
+    if (hipMemsetAsync(grad_out, 0, (size_t)W.n_gcn * 4u, st) != hipSuccess) return SG_ERR_HIP;
+    return web_status();
+  }
+  if (!params || !g_emb || !workspace || ld_g < W.D) return SG_ERR_ARG;
+  // one gradient row per workgroup of the backward instance kernel (gcn_launch: one per CU)
+  const int rows = sg_num_cus();
+  if (rows < 1 || rows > kWebBwdRows) return SG_ERR_UNSUPPORTED;
+  (void)hipGetLastError();   // report only this call's launch errors
+  const WebEmbBwdWs ws = web_emb_bwd_ws(W, count, true);
+  float *base = (float *)(((uintptr_t)workspace + 15u) & ~(uintptr_t)15u);   // 16-byte D2 rows
+  float *slab = base + ws.SLAB, *X = base + ws.X, *GXs = base + ws.GX, *D2 = base + ws.D2;
+  uint16_t *MASK = (uint16_t *)(base + ws.MASK);
+  int32_t *ids = (int32_t *)(base + ws.IDS), *emb = (int32_t *)(base + ws.EMB);
+  if (hipMemsetAsync(slab, 0, (size_t)rows * W.n_gcn * 4u, st) != hipSuccess) return SG_ERR_HIP;
+  // ws.cc is even whenever a second chunk follows: no unit straddles two chunks
+  for (int64_t c0 = 0; c0 < count; c0 += ws.cc) {
+    const int64_t cn = count - c0 < ws.cc ? count - c0 : ws.cc;
+    const int32_t *gidx = graph_idx ? graph_idx + c0 : ids;
+    if (!graph_idx)
+      hipLaunchKernelGGL(web_embed_iota_kernel, dim3((unsigned)((cn + 255) / 256)), dim3(256), 0,
+                         st, ids, cn, c0);
+    // the masked forward with the keep bits and D2 rows stored (X: not used)
+    const WebDrop drop = {sg_seed_key(seed), (entry_offset + c0) >> 1};
+    GcnArgs G;
+    if ((rc = web_embed_forward(W, store, gidx, cn, params, X, MASK, D2, status_out, emb, st,
+                                &G, &drop)) != SG_OK)
+      return rc;
+    hipLaunchKernelGGL(web_drop_rows_in_kernel, dim3((unsigned)((cn + 3) / 4)), dim3(256), 0, st,
+                       g_emb + c0 * ld_g, ld_g, cn, G.Cp, W.D, W.Dp, GXs);
+    G.GX = GXs;
     G.slab = slab;
     if ((rc = gcn_launch(true, W, G, 2 * cn, st)) != SG_OK) return rc;
   }

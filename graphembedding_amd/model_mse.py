@@ -138,7 +138,7 @@ class GridProblem:
     dropout: Optional[str] = None   # None: dropout 0 only; 'graph': one mask set per graph
     # graph-store (Web) problems (web_grid_problem): store_dev is (CsrStore, its device
     # struct), the embedding buffers are [*][ld] (ld = D rounded up to 128)
-    ws_fwd: object = None           # workspace of sg_web_embed
+    ws_fwd: object = None           # workspace of sg_web_embed / sg_web_embed_drop
 
     def check(self):
         """Raise if a kernel reported a bad graph id or node count (synchronises)."""
@@ -859,16 +859,20 @@ class SiameseGCNTNMSE(object):
         return float(self.loss_buf[0].item() + self.reg_buf[0].item())
 
     # ---- embed-once training for graph-store models
-    # (include/siamese_web_embed_train.h: dropout 0 only) ----
-    def web_grid_problem(self, store, labels, q_idx=None, db_idx=None, y_stats=None):
+    # (include/siamese_web_embed_train.h: dropout 0 only;
+    # include/siamese_web_embed_drop.h: dropout='graph', masks keyed per graph) ----
+    def web_grid_problem(self, store, labels, q_idx=None, db_idx=None, y_stats=None,
+                         dropout=None):
         """grid_problem for a graph-store (Web) model: the device-resident state of an m x n
         block of pairs over a web.CsrStore (query q_idx[i] as graph 1, database db_idx[j] as
         graph 2; None = every store graph) with labels [m][n].  The embedding buffers keep
         the [*][ld] rows of sg_web_embed (ld = D rounded up to 128).  Build once, step many
-        times (web_grid_fwd_bwd / web_grid_train_step).  Needs flags.dropout = 0."""
+        times (web_grid_fwd_bwd / web_grid_train_step).
+        dropout: None serves flags.dropout = 0 only; 'graph' trains with dropout masks keyed
+        per graph (web_grid_fwd_bwd) and is stored on the problem."""
         torch = self.torch
         self._only_web('web_grid_problem')
-        self._no_dropout('web_grid_problem')
+        self._grid_dropout(dropout, 'web_grid_problem')
         self.check_node_counts(store.n, 'web_grid_problem')
         G = len(store)
         if G == 0 or int(np.asarray(store.n).min()) < 1:
@@ -903,12 +907,16 @@ class SiameseGCNTNMSE(object):
             emb=torch.empty((U, ld), **f32), g_emb=torch.zeros((U, ld), **f32),
             g_q=torch.zeros((m, ld), **f32), g_db=torch.zeros((n, ld), **f32),
             status=torch.zeros(1, dtype=torch.int32, device=dev),
-            ws_grid=ws(_lib.web_score_grid_bwd_workspace_bytes(self.sg, m, n)),
-            ws_embed=ws(_lib.web_embed_bwd_workspace_bytes(self.sg, U)),
-            ws_fwd=ws(_lib.web_embed_workspace_bytes(self.sg, U)))
+            ws_grid=ws(_lib.web_score_grid_bwd_workspace_bytes(
+                self._sg_keep1() if dropout else self.sg, m, n)),
+            ws_embed=ws(_lib.web_embed_drop_bwd_workspace_bytes(self.sg, U) if dropout else
+                        _lib.web_embed_bwd_workspace_bytes(self.sg, U)),
+            ws_fwd=ws(_lib.web_embed_drop_workspace_bytes(self.sg, U) if dropout else
+                      _lib.web_embed_workspace_bytes(self.sg, U)),
+            dropout=dropout)
 
     def web_grid_fwd_bwd(self, store, labels=None, q_idx=None, db_idx=None, add_label_term=True,
-                         s_out=None):
+                         s_out=None, dropout=None, seed=None):
         """grid_fwd_bwd for a graph-store (Web) model: every distinct graph's CSR node stack
         runs forward once (sg_web_embed), the large-D NTN grid runs forward and backward
         (sg_web_score_grid_fwd_bwd), the query-role and database-role gradients of each graph
@@ -916,17 +924,40 @@ class SiameseGCNTNMSE(object):
         Σ∂loss_mse/∂θ in self.grad and loss_mse in self.loss_buf[0] where fwd_bwd over the
         m·n pairs (web_batch, batch_total = m·n) leaves them, up to fp32 summation order.
         store: a web.CsrStore with labels [m][n], or a web_grid_problem(...) built once.
-        s_out: [m][n] pre-activation scores, optional.  Needs flags.dropout = 0."""
+        s_out: [m][n] pre-activation scores, optional.  With dropout=None it needs
+        flags.dropout = 0.
+
+        dropout='graph' (given here, or stored on the web_grid_problem) trains with dropout,
+        the masks keyed per graph exactly as grid_fwd_bwd does for the other paths: distinct
+        graph c of the step (ascending store id) is embedded as side c & 1 of unit c >> 1
+        under the step's seed (seed, default the train steps' seed of step_count) with the
+        masks the pair kernel draws for that pair and side (sg_web_embed_drop); the grid runs
+        on the masked embeddings with keep_prob 1, and sg_web_embed_drop_bwd takes the summed
+        role gradients back under the same masks.  One mask set per graph per step: not the
+        reference's per-pair masks (quirk A4), so the loss and gradient are not those of
+        fwd_bwd over the m·n pairs.  At flags.dropout = 0 it equals dropout=None."""
         self._only_web('web_grid_fwd_bwd')
-        self._no_dropout('web_grid_fwd_bwd')
-        gp = store if isinstance(store, GridProblem) else self.web_grid_problem(
-            store, labels, q_idx, db_idx)
+        if isinstance(store, GridProblem):
+            gp = store
+            if dropout is not None and dropout != gp.dropout:
+                raise _lib.SiameseHipError('web_grid_fwd_bwd: dropout={!r} on a web_grid_problem '
+                                           'built with dropout={!r}'.format(dropout, gp.dropout))
+            self._grid_dropout(gp.dropout, 'web_grid_fwd_bwd')
+        else:
+            self._grid_dropout(dropout, 'web_grid_fwd_bwd')
+            gp = self.web_grid_problem(store, labels, q_idx, db_idx, dropout=dropout)
         if gp.ws_fwd is None:
             raise _lib.SiameseHipError('web_grid_fwd_bwd: the problem was built by grid_problem; '
                                        'use web_grid_problem')
         sg, csr = self.sg, gp.store_dev[1]
         U, ld = int(gp.uniq.numel()), int(gp.emb.shape[1])
-        _lib.web_embed(sg, csr, gp.uniq, U, self.params, gp.emb, gp.ws_fwd, gp.status)
+        if gp.dropout:
+            seed = self._seed(seed)
+            sg = self._sg_keep1()   # the grid's model: the masks are in the embeddings
+            _lib.web_embed_drop(self.sg, csr, gp.uniq, U, 0, self.params, seed, gp.emb,
+                                gp.ws_fwd, gp.status)
+        else:
+            _lib.web_embed(sg, csr, gp.uniq, U, self.params, gp.emb, gp.ws_fwd, gp.status)
         eq, edb = (gp.emb, gp.emb) if gp.identity else (gp.emb[gp.q_pos], gp.emb[gp.db_pos])
         _lib.web_score_grid_fwd_bwd(sg, eq, ld, edb, ld, gp.m, gp.n, self.params, gp.labels,
                                     gp.n, gp.m * gp.n, gp.y_stats, add_label_term, s_out, gp.n,
@@ -938,15 +969,21 @@ class SiameseGCNTNMSE(object):
             gp.g_emb.zero_()
             gp.g_emb.index_add_(0, gp.q_pos, gp.g_q)
             gp.g_emb.index_add_(0, gp.db_pos, gp.g_db)
-        _lib.web_embed_bwd(sg, csr, gp.uniq, U, self.params, gp.g_emb, ld, self.grad,
-                           gp.ws_embed, gp.status)
+        if gp.dropout:
+            _lib.web_embed_drop_bwd(self.sg, csr, gp.uniq, U, 0, self.params, seed, gp.g_emb, ld,
+                                    self.grad, gp.ws_embed, gp.status)
+        else:
+            _lib.web_embed_bwd(sg, csr, gp.uniq, U, self.params, gp.g_emb, ld, self.grad,
+                               gp.ws_embed, gp.status)
         return gp
 
-    def web_grid_train_step(self, store, labels=None, q_idx=None, db_idx=None, sync=True):
+    def web_grid_train_step(self, store, labels=None, q_idx=None, db_idx=None, sync=True,
+                            dropout=None):
         """web_grid_fwd_bwd followed by Adam: train_step's embed-once counterpart for
         graph-store models (same loss return: loss_mse + weight decay at the pre-update
-        parameters)."""
-        self.web_grid_fwd_bwd(store, labels, q_idx, db_idx)
+        parameters).  With dropout='graph' every step draws new masks (the seed follows
+        step_count)."""
+        self.web_grid_fwd_bwd(store, labels, q_idx, db_idx, dropout=dropout)
         if self.grad_hook is not None:
             self.grad_hook(self)
         self.apply_adam()

@@ -12,12 +12,15 @@ dataset in CSR form and hands the kernels pair ids:
                   kernels skip feature tiles beyond every pair's node count).
   WebAllPairs     one rank's shard of the all-pairs stream on the graph store
                   (the C5 bench workload), stepped through sg_web_fwd_bwd.
+  WebAllPairsGrid the all-pairs step embed-once (model.web_grid_fwd_bwd): G node
+                  stacks and the NTN grid instead of G² pair bodies.
 
 Dropout masks are keyed by the pair's position in the (ordered) list plus
 pair_offset, exactly like the record path's keys.
 """
 from __future__ import annotations
 
+import weakref
 from typing import Optional, Sequence
 
 import numpy as np
@@ -165,3 +168,47 @@ class WebAllPairs(object):
     def batch(self, model):
         return model.web_batch(self.store, self.pairs, self.labels, pair_offset=self.start,
                                batch_total=self.total, y_stats=self.y_stats, chunk=self.chunk)
+
+
+class WebAllPairsGrid(object):
+    """The all-pairs step embed-once on the graph store: allpairs.AllPairsGrid's counterpart
+    for model.web_grid_fwd_bwd (dropout=None: flags.dropout = 0 only; dropout='graph': one
+    dropout mask set per graph per step).  gs: a GraphSet, whose CsrStore is built the way
+    WebAllPairs builds it, or a CsrStore.  Holds the G x G label matrix and its y_stats on the
+    device; a step embeds the G graphs once, runs the NTN grid forward + backward and one
+    node-stack backward per graph instead of G² pair bodies
+    (include/siamese_web_embed_train.h, include/siamese_web_embed_drop.h).  Same loss and
+    gradient as WebAllPairs' batch through fwd_bwd at dropout 0, up to fp32 summation order."""
+
+    def __init__(self, gs, labels: np.ndarray, device='cuda', dropout=None,
+                 d_in: Optional[int] = None, n_cap: Optional[int] = None):
+        import torch
+        self.store = gs if isinstance(gs, CsrStore) else CsrStore(
+            gs.mgs, d_in if d_in is not None else gs.d_in, n_cap)
+        G = len(self.store)
+        lab = np.ascontiguousarray(np.asarray(labels, np.float32).reshape(G, G))
+        self.total = G * G
+        self.labels = torch.from_numpy(lab).to(device)
+        y = lab.reshape(-1).astype(np.float64)
+        ybar = y.mean() if y.size else 0.0
+        self.y_stats = torch.tensor([ybar, 0.5 * ((y - ybar) ** 2).sum()], dtype=torch.float32,
+                                    device=device)
+        self.dropout = dropout
+        self._problem = None
+        self._owner = None
+
+    def problem(self, model):
+        """The model's web_grid_problem of this grid (built once per model)."""
+        owner = self._owner() if self._owner is not None else None
+        if owner is not model:
+            self._problem = model.web_grid_problem(self.store, self.labels,
+                                                   y_stats=self.y_stats, dropout=self.dropout)
+            self._owner = weakref.ref(model)
+        return self._problem
+
+    def fwd_bwd(self, model, add_label_term: bool = True):
+        """Leaves the gradient / loss_mse in model.grad / model.loss_buf."""
+        model.web_grid_fwd_bwd(self.problem(model), add_label_term=add_label_term)
+
+    def train_step(self, model, sync: bool = True):
+        return model.web_grid_train_step(self.problem(model), sync=sync)
