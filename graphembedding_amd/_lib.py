@@ -263,6 +263,14 @@ def lib():
         L.sg_web_embed_drop_bwd.argtypes = [pm, pc, vp, c_i64, c_i64, vp, c_u64, vp, c_i64, vp,
                                             vp, vp, vp]
         L.sg_web_embed_drop_bwd.restype = c_i32
+    # device-side evaluation of the test matrix (include/siamese_eval.h); a library without
+    # it still loads
+    if all(hasattr(L, s) for s in EVAL_SYMBOLS):
+        L.sg_eval_rows_workspace_bytes.argtypes = [c_i64, c_i64, c_i32]
+        L.sg_eval_rows_workspace_bytes.restype = c_i64
+        L.sg_eval_rows.argtypes = [vp, c_i64, c_i64, c_i64, vp, vp, ctypes.POINTER(c_i32), c_i32,
+                                   vp, vp, vp, vp, vp, vp]
+        L.sg_eval_rows.restype = c_i32
     _lib = L
     return L
 
@@ -318,6 +326,10 @@ WEB_EMBED_TRAIN_SYMBOLS = ('sg_web_score_grid_bwd_workspace_bytes', 'sg_web_scor
 # with graph-keyed dropout masks; detected by presence)
 WEB_EMBED_DROP_SYMBOLS = ('sg_web_embed_drop_workspace_bytes', 'sg_web_embed_drop',
                           'sg_web_embed_drop_bwd_workspace_bytes', 'sg_web_embed_drop_bwd')
+
+# the symbols of include/siamese_eval.h (device-side evaluation of the test matrix: the
+# per-row counts behind ap@k and MRR and the squared-error sums; detected by presence)
+EVAL_SYMBOLS = ('sg_eval_rows_workspace_bytes', 'sg_eval_rows')
 
 # class_start entries of sg_pair_order_cls (include/siamese_hip.h SG_FAST_CLASSES_P1)
 FAST_CLASSES_P1 = 5
@@ -859,6 +871,36 @@ def web_search_topk(m: SgModel, emb_q, ld_q, emb_db, ld_db, n_q, n_db, params, a
                                    int(bool(apply_final)), int(k), int(bool(largest)),
                                    int(seg_cols), _ptr(idx_out), _ptr(val_out), _ptr(workspace),
                                    _stream(stream)), 'sg_web_search_topk')
+
+
+def _eval_fn(name: str):
+    fn = getattr(lib(), name, None)
+    if fn is None or fn.argtypes is None:
+        raise SiameseHipError(name + ': this libsiamese_hip.so has no include/siamese_eval.h '
+                              'entry points')
+    return fn
+
+
+def eval_workspace_bytes(n_q: int, n_db: int, n_ks: int) -> int:
+    b = int(_eval_fn('sg_eval_rows_workspace_bytes')(int(n_q), int(n_db), int(n_ks)))
+    if b < 0:
+        raise SiameseHipError('sg_eval_rows_workspace_bytes: the evaluation serves rows of 2 <= '
+                              'n <= 32768 columns, at most 2^29 rows and 1 .. min(16, n - 1) '
+                              "k's")
+    return b
+
+
+def eval_rows(scores, n_q, n_db, ld, true_rank, true_sim, ks, hits_out, best_rank_out, sqerr_out,
+              nan_out, workspace=None, stream=None):
+    """sg_eval_rows: per query row the ap@k hit counts, the best predicted rank among the true
+    top-1 graphs, the float64 squared-error sum (true_sim / sqerr_out both None: skipped) and
+    the NaN count; ks is a host sequence of strictly ascending k's."""
+    ks = [int(k) for k in ks]
+    ks_arr = (ctypes.c_int32 * max(len(ks), 1))(*ks)
+    check(_eval_fn('sg_eval_rows')(
+        _ptr(scores), int(n_q), int(n_db), int(ld), _ptr(true_rank), _ptr(true_sim), ks_arr,
+        len(ks), _ptr(hits_out), _ptr(best_rank_out), _ptr(sqerr_out), _ptr(nan_out),
+        _ptr(workspace), _stream(stream)), 'sg_eval_rows')
 
 
 def seed_advance(seed_dev, delta=1, stream=None):

@@ -68,6 +68,11 @@ DEFAULTS: Dict[str, Any] = dict(
     # once and fill the matrix with the NTN score grid (siamese_embed.h: inference mode,
     # dropout off)
     test_path='pairs',
+    # where train.test turns the matrix into ap@k / MRR / mse: 'host' = Eval.eval_test
+    # (metrics.py over results.py's sorts) | 'device' = Eval.eval_test_device (one
+    # sg_eval_rows launch per norm over the device matrix; needs test_path='embed' and
+    # test_matrix='full')
+    eval_path='host',
     n_max=None,                # record node capacity (default: Padding max_in_dims or data max)
     record_dtype='f32',        # storage of Â in pair records: 'f32' | 'bf16' (config C3); fp32 math
     seed=123,                  # dropout RNG base seed (the reference's TF RNG was unseeded)

@@ -58,3 +58,25 @@ class Eval(object):
             out['time'] = {cur_model: metrics.average_time(pred)}
         self.results.update(out)
         return self.results
+
+    def eval_test_device(self, cur_model, scores, time_mat):
+        """eval_test for a float32 DEVICE score matrix: the same keys and nesting, computed
+        by sg_eval_rows (device_eval.py) instead of the host's sorts.  No Result object is
+        built for cur_model, so self.rs gets no entry for it."""
+        from . import device_eval
+        truth = getattr(self, '_truth', None)
+        if truth is None or truth.device != scores.device:
+            truth = device_eval.TruthTable(self.true_result, self.sim_kernel_name, self.yeta,
+                                           scores.device)
+            self._truth = truth
+        out = {}
+        for norm in (True, False):
+            sfx = '_norm' if norm else '_nonorm'
+            aps, mrr, mse = device_eval.eval_rows(scores, truth, norm)
+            out['apk' + sfx] = {cur_model: {'ks': list(truth.ks), 'aps': aps}}
+            out['mrr' + sfx] = {cur_model: mrr}
+            out['mse' + sfx] = {cur_model: mse}
+        if time_mat is not None:
+            out['time'] = {cur_model: np.mean(np.asarray(time_mat))}
+        self.results.update(out)
+        return self.results

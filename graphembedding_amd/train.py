@@ -72,6 +72,15 @@ def test(data, dist_calculator, model, flags=None, evaluator=None, verbose=True)
     f = flags or FLAGS
     m, n = data.m_n()
     test_path = getattr(f, 'test_path', 'pairs')
+    eval_path = getattr(f, 'eval_path', 'host')
+    if eval_path == 'device':
+        # the pairs path applies its final activation on the host and compat_diag builds its
+        # matrix there: neither has a bit-equal device matrix to evaluate
+        if test_path != 'embed' or f.test_matrix == 'compat_diag':
+            raise RuntimeError("eval_path='device' needs test_path='embed' and "
+                               "test_matrix='full'")
+    elif eval_path != 'host':
+        raise RuntimeError('Unknown eval_path {}'.format(eval_path))
     if test_path == 'embed':
         return _test_embed(data, model, f, evaluator, verbose)
     if test_path != 'pairs':
@@ -145,10 +154,11 @@ def _test_embed(data, model, f, evaluator, verbose):
     elapsed = _time.time() - t0
     sims = s.cpu().numpy().astype(np.float64)
     time_mat = np.full((m, n), elapsed * 1000.0 / max(1, m * n))   # msec per pair
-    return _test_results(f, sims, time_mat, time_mode, elapsed, evaluator, verbose)
+    scores_dev = s if getattr(f, 'eval_path', 'host') == 'device' else None
+    return _test_results(f, sims, time_mat, time_mode, elapsed, evaluator, verbose, scores_dev)
 
 
-def _test_results(f, sims, time_mat, time_mode, elapsed, evaluator, verbose):
+def _test_results(f, sims, time_mat, time_mode, elapsed, evaluator, verbose, scores_dev=None):
     m, n = sims.shape
     if f.test_matrix == 'compat_diag':
         sim_mat = np.zeros((m, n))
@@ -158,10 +168,13 @@ def _test_results(f, sims, time_mat, time_mode, elapsed, evaluator, verbose):
         sim_mat = sims
     results = None
     if evaluator is not None:
-        results = evaluator.eval_test(f.model, sim_mat, time_mat)
+        if scores_dev is not None:   # eval_path='device': sim_mat is scores_dev on the host
+            results = evaluator.eval_test_device(f.model, scores_dev, time_mat)
+        else:
+            results = evaluator.eval_test(f.model, sim_mat, time_mat)
+            evaluator.rs[f.model].time_mat_mode = time_mode
         # the deviation is stated on the result: 'batched' entries are a launch average
         results['time_mat_mode'] = {f.model: time_mode}
-        evaluator.rs[f.model].time_mat_mode = time_mode
     if verbose:
         print('scored {}x{} pairs in {}'.format(m, n, print_msec(elapsed)))
     return sim_mat, time_mat, results
