@@ -150,3 +150,36 @@ def check_grad_per_var(g_gpu, g_ref, layers, d_in, tol=1e-4, what=''):
     assert off == g_ref.size
     assert not bad, '{} per-variable gradient errors above {}: {}'.format(what, tol, bad)
     return rel
+
+
+def _check_pairs(store, pairs, labels, D, d_in, params, seed, keep, yeta, ybar, offset,
+                 block):
+    """The C restatement over `pairs` (global keys offset + i), in blocks of host records
+    (capacity-D records of 4M pairs would not fit host memory at once)."""
+    from concurrent.futures import ThreadPoolExecutor
+    from oracle import cpu_ref
+    P = pairs.shape[0]
+    s = np.empty(P, np.float32)
+    g = None
+    loss = 0.0
+    th = cpu_ref.default_threads()
+    starts = list(range(0, P, block))
+
+    def pack(b0):
+        b1 = min(P, b0 + block)
+        return store.pack_host(pairs[b0:b1], labels[b0:b1], dtype='f32')
+
+    # pack block i + 1 on a helper thread while the C port (GIL released) runs block i
+    with ThreadPoolExecutor(1) as ex:
+        nxt = ex.submit(pack, starts[0]) if starts else None
+        for i, b0 in enumerate(starts):
+            words = nxt.result()
+            nxt = ex.submit(pack, starts[i + 1]) if i + 1 < len(starts) else None
+            sb, gb, lb = cpu_ref.fwd_bwd_records(words, D, d_in, params, seed, keep, yeta,
+                                                 ybar, pair_offset=offset + b0, threads=th,
+                                                 f64_acc=True)
+            s[b0:b0 + sb.shape[0]] = sb
+            g = gb.astype(np.float64) if g is None else g + gb
+            loss += lb
+            del words
+    return s, g, loss

@@ -24,8 +24,7 @@ import os
 import numpy as np
 import pytest
 
-from _fixtures import check_grad_per_var
-from oracle import cpu_ref
+from _fixtures import _check_pairs, check_grad_per_var
 
 pytestmark = pytest.mark.gpu
 
@@ -36,38 +35,6 @@ C4_FLAGS = dict(layer_3='Padding:max_in_dims=30,padding_value=0',
 WEB_FLAGS = dict(layer_3='Padding:max_in_dims=512,padding_value=0',
                  layer_4='NTN:input_dim=512,feature_map_dim=10,inneract=relu,dropout=True,'
                          'bias=True')
-
-
-def _check_pairs(store, pairs, labels, D, d_in, params, seed, keep, yeta, ybar, offset,
-                 block):
-    """The C restatement over `pairs` (global keys offset + i), in blocks of host records
-    (capacity-D records of 4M pairs would not fit host memory at once)."""
-    from concurrent.futures import ThreadPoolExecutor
-    P = pairs.shape[0]
-    s = np.empty(P, np.float32)
-    g = None
-    loss = 0.0
-    th = cpu_ref.default_threads()
-    starts = list(range(0, P, block))
-
-    def pack(b0):
-        b1 = min(P, b0 + block)
-        return store.pack_host(pairs[b0:b1], labels[b0:b1], dtype='f32')
-
-    # pack block i + 1 on a helper thread while the C port (GIL released) runs block i
-    with ThreadPoolExecutor(1) as ex:
-        nxt = ex.submit(pack, starts[0]) if starts else None
-        for i, b0 in enumerate(starts):
-            words = nxt.result()
-            nxt = ex.submit(pack, starts[i + 1]) if i + 1 < len(starts) else None
-            sb, gb, lb = cpu_ref.fwd_bwd_records(words, D, d_in, params, seed, keep, yeta,
-                                                 ybar, pair_offset=offset + b0, threads=th,
-                                                 f64_acc=True)
-            s[b0:b0 + sb.shape[0]] = sb
-            g = gb.astype(np.float64) if g is None else g + gb
-            loss += lb
-            del words
-    return s, g, loss
 
 
 @pytest.mark.timeout(900)
