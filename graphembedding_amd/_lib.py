@@ -271,6 +271,22 @@ def lib():
         L.sg_eval_rows.argtypes = [vp, c_i64, c_i64, c_i64, vp, vp, ctypes.POINTER(c_i32), c_i32,
                                    vp, vp, vp, vp, vp, vp]
         L.sg_eval_rows.restype = c_i32
+    # embed-once retrieval, search and training for the Dot head (include/siamese_dot_embed.h);
+    # a library without them still loads
+    if all(hasattr(L, s) for s in DOT_EMBED_SYMBOLS):
+        L.sg_dot_score_grid.argtypes = [pm, vp, c_i64, vp, c_i64, c_i64, c_i64, c_i32, vp, c_i64,
+                                        vp]
+        L.sg_dot_score_grid.restype = c_i32
+        L.sg_dot_search_topk_workspace_bytes.argtypes = [pm, c_i64, c_i64, c_i32, c_i64]
+        L.sg_dot_search_topk_workspace_bytes.restype = c_i64
+        L.sg_dot_search_topk.argtypes = [pm, vp, c_i64, vp, c_i64, c_i64, c_i64, c_i32, c_i32,
+                                         c_i32, c_i64, vp, vp, vp, vp]
+        L.sg_dot_search_topk.restype = c_i32
+        L.sg_dot_score_grid_bwd_workspace_bytes.argtypes = [pm, c_i64, c_i64]
+        L.sg_dot_score_grid_bwd_workspace_bytes.restype = c_i64
+        L.sg_dot_score_grid_fwd_bwd.argtypes = [pm, vp, c_i64, vp, c_i64, c_i64, c_i64, vp, c_i64,
+                                                c_i64, vp, c_i32, vp, c_i64, vp, vp, vp, vp, vp]
+        L.sg_dot_score_grid_fwd_bwd.restype = c_i32
     _lib = L
     return L
 
@@ -330,6 +346,12 @@ WEB_EMBED_DROP_SYMBOLS = ('sg_web_embed_drop_workspace_bytes', 'sg_web_embed_dro
 # the symbols of include/siamese_eval.h (device-side evaluation of the test matrix: the
 # per-row counts behind ap@k and MRR and the squared-error sums; detected by presence)
 EVAL_SYMBOLS = ('sg_eval_rows_workspace_bytes', 'sg_eval_rows')
+
+# the symbols of include/siamese_dot_embed.h (embed-once retrieval, search and training for the
+# Dot head: the score grid E_q · E_dbᵀ, its fused top-k and its adjoint; detected by presence)
+DOT_EMBED_SYMBOLS = ('sg_dot_score_grid', 'sg_dot_search_topk_workspace_bytes',
+                     'sg_dot_search_topk', 'sg_dot_score_grid_bwd_workspace_bytes',
+                     'sg_dot_score_grid_fwd_bwd')
 
 # class_start entries of sg_pair_order_cls (include/siamese_hip.h SG_FAST_CLASSES_P1)
 FAST_CLASSES_P1 = 5
@@ -871,6 +893,67 @@ def web_search_topk(m: SgModel, emb_q, ld_q, emb_db, ld_db, n_q, n_db, params, a
                                    int(bool(apply_final)), int(k), int(bool(largest)),
                                    int(seg_cols), _ptr(idx_out), _ptr(val_out), _ptr(workspace),
                                    _stream(stream)), 'sg_web_search_topk')
+
+
+_NO_DOT = ('the Dot grid serves models whose pair head is Dot, off the graph-store path, with '
+           'an embedding of at most 512 floats')
+
+
+def _dot_fn(name: str):
+    fn = getattr(lib(), name, None)
+    if fn is None or fn.argtypes is None:
+        raise SiameseHipError(name + ': this libsiamese_hip.so has no '
+                              'include/siamese_dot_embed.h entry points')
+    return fn
+
+
+def dot_score_grid(m: SgModel, emb_q, ld_q, emb_db, ld_db, n_q, n_db, apply_final, out, ld_out,
+                   stream=None):
+    """sg_dot_score_grid: out[i][j] = Σ_a emb_q[i][a] · emb_db[j][a] (final activation applied
+    when apply_final); no params and no workspace."""
+    check(_dot_fn('sg_dot_score_grid')(
+        ctypes.byref(m), _ptr(emb_q), int(ld_q), _ptr(emb_db), int(ld_db), int(n_q), int(n_db),
+        int(bool(apply_final)), _ptr(out), int(ld_out), _stream(stream)), 'sg_dot_score_grid')
+
+
+def dot_search_workspace_bytes(m: SgModel, n_q: int, n_db: int, k: int, seg_cols: int = 0) -> int:
+    b = int(_dot_fn('sg_dot_search_topk_workspace_bytes')(ctypes.byref(m), int(n_q), int(n_db),
+                                                          int(k), int(seg_cols)))
+    if b < 0:
+        raise SiameseHipError('sg_dot_search_topk_workspace_bytes: ' + _NO_DOT + ', 1 <= k <= '
+                              'min(n, 64) and seg_cols = 0 or a positive multiple of 64')
+    return b
+
+
+def dot_search_topk(m: SgModel, emb_q, ld_q, emb_db, ld_db, n_q, n_db, apply_final, k, largest,
+                    seg_cols, idx_out, val_out, workspace, stream=None):
+    """sg_dot_search_topk: what dot_score_grid + topk_rows return, without the [n_q][n_db]
+    matrix."""
+    check(_dot_fn('sg_dot_search_topk')(
+        ctypes.byref(m), _ptr(emb_q), int(ld_q), _ptr(emb_db), int(ld_db), int(n_q), int(n_db),
+        int(bool(apply_final)), int(k), int(bool(largest)), int(seg_cols), _ptr(idx_out),
+        _ptr(val_out), _ptr(workspace), _stream(stream)), 'sg_dot_search_topk')
+
+
+def dot_score_grid_bwd_workspace_bytes(m: SgModel, n_q: int, n_db: int) -> int:
+    b = int(_dot_fn('sg_dot_score_grid_bwd_workspace_bytes')(ctypes.byref(m), int(n_q),
+                                                             int(n_db)))
+    if b < 0:
+        raise SiameseHipError('sg_dot_score_grid_bwd_workspace_bytes: ' + _NO_DOT +
+                              ', without effective dropout')
+    return b
+
+
+def dot_score_grid_fwd_bwd(m: SgModel, emb_q, ld_q, emb_db, ld_db, n_q, n_db, labels, ld_labels,
+                           batch_total, y_stats, add_label_term, s_out, ld_s, g_emb_q, g_emb_db,
+                           loss_out, workspace, stream=None):
+    """sg_dot_score_grid_fwd_bwd: scores, loss and the embeddings' gradients g_emb_q [n_q][E],
+    g_emb_db [n_db][E] of the Dot head over the grid (the head has no variables)."""
+    check(_dot_fn('sg_dot_score_grid_fwd_bwd')(
+        ctypes.byref(m), _ptr(emb_q), int(ld_q), _ptr(emb_db), int(ld_db), int(n_q), int(n_db),
+        _ptr(labels), int(ld_labels), int(batch_total), _ptr(y_stats),
+        int(bool(add_label_term)), _ptr(s_out), int(ld_s), _ptr(g_emb_q), _ptr(g_emb_db),
+        _ptr(loss_out), _ptr(workspace), _stream(stream)), 'sg_dot_score_grid_fwd_bwd')
 
 
 def _eval_fn(name: str):

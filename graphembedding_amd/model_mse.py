@@ -536,6 +536,25 @@ class SiameseGCNTNMSE(object):
                                        'web_search / topk'.format(what))
 
     @property
+    def is_dot(self) -> bool:
+        """The pair head is Dot (layers.py:230-252): the grid calls of
+        include/siamese_dot_embed.h serve it, the NTN grid calls every other model."""
+        return self.layers[-1]['kind'] == 'Dot'
+
+    def _dot_rows(self, e, what):
+        """(tensor, row stride) of embeddings [*, E] as the Dot grid calls take them: a tensor
+        with unit inner stride and a row stride >= E is passed on as it is, anything else is
+        copied."""
+        torch = self.torch
+        d = self.embed_dim
+        e = torch.as_tensor(e, dtype=torch.float32, device=self.device)
+        if e.dim() != 2 or e.shape[1] != d:
+            raise _lib.SiameseHipError('{}: embeddings must be [*, {}]'.format(what, d))
+        if e.stride(1) != 1 or (e.shape[0] > 1 and e.stride(0) < d):
+            e = e.contiguous()
+        return e, (int(e.stride(0)) if e.shape[0] > 1 else max(d, int(e.stride(0))))
+
+    @property
     def embed_dim(self) -> int:
         """Width of one graph embedding: the pair head's per-graph input."""
         self._no_web('embed_dim')
@@ -568,6 +587,12 @@ class SiameseGCNTNMSE(object):
         pre-activation score of pred_sim_without_act."""
         torch = self.torch
         self._no_web('score_grid')
+        if self.is_dot:
+            (q, ld_q), (db, ld_db) = (self._dot_rows(e, 'score_grid') for e in (emb_q, emb_db))
+            m, n = int(q.shape[0]), int(db.shape[0])
+            out = torch.empty((m, n), dtype=torch.float32, device=self.device)
+            _lib.dot_score_grid(self.sg, q, ld_q, db, ld_db, m, n, final, out, n)
+            return out
         d = self.embed_dim
         q = torch.as_tensor(emb_q, dtype=torch.float32, device=self.device).contiguous()
         db = torch.as_tensor(emb_db, dtype=torch.float32, device=self.device).contiguous()
@@ -601,6 +626,19 @@ class SiameseGCNTNMSE(object):
         library's choice; the result does not depend on it."""
         torch = self.torch
         self._no_web('search')
+        if self.is_dot:
+            (q, ld_q), (db, ld_db) = (self._dot_rows(e, 'search') for e in (emb_q, emb_db))
+            m, n = int(q.shape[0]), int(db.shape[0])
+            nbytes = _lib.dot_search_workspace_bytes(self.sg, m, n, k, seg_cols)
+            ws = getattr(self, '_search_ws', None)      # the last workspace, kept while it fits
+            if ws is None or ws.numel() * 4 < nbytes or ws.device != q.device:
+                ws = torch.empty(nbytes // 4 + 1, dtype=torch.float32, device=self.device)
+                self._search_ws = ws
+            idx = torch.empty((m, int(k)), dtype=torch.int32, device=self.device)
+            val = torch.empty((m, int(k)), dtype=torch.float32, device=self.device)
+            _lib.dot_search_topk(self.sg, q, ld_q, db, ld_db, m, n, final, k, largest, seg_cols,
+                                 idx, val, ws)
+            return idx, val
         d = self.embed_dim
         q = torch.as_tensor(emb_q, dtype=torch.float32, device=self.device).contiguous()
         db = torch.as_tensor(emb_db, dtype=torch.float32, device=self.device).contiguous()
@@ -779,7 +817,8 @@ class SiameseGCNTNMSE(object):
             emb=torch.empty((U, E), **f32), g_emb=torch.empty((U, E), **f32),
             g_q=torch.empty((m, E), **f32), g_db=torch.empty((n, E), **f32),
             status=torch.zeros(1, dtype=torch.int32, device=dev),
-            ws_grid=ws(_lib.score_grid_bwd_workspace_bytes(
+            ws_grid=ws((_lib.dot_score_grid_bwd_workspace_bytes if self.is_dot else
+                        _lib.score_grid_bwd_workspace_bytes)(
                 self._sg_keep1() if dropout else self.sg, m, n)),
             ws_embed=ws(_lib.embed_drop_bwd_workspace_bytes(self.sg, U) if dropout else
                         _lib.embed_bwd_workspace_bytes(self.sg, U)),
@@ -795,7 +834,10 @@ class SiameseGCNTNMSE(object):
         self.loss_buf[0] exactly where fwd_bwd over the m·n pairs (batch_total = m·n) leaves
         them, up to fp32 summation order.  store: a GraphStore with labels [m][n], or a
         grid_problem(...) built once.  s_out: [m][n] pre-activation scores, optional.
-        Needs the NTN head the score grid serves and, with dropout=None, flags.dropout = 0.
+        Needs the NTN head the score grid serves, or the Dot head (the grid call is then
+        sg_dot_score_grid_fwd_bwd, include/siamese_dot_embed.h: no head variables, the
+        node-stack backward writes the whole gradient) and, with dropout=None,
+        flags.dropout = 0.
 
         dropout='graph' (given here, or stored on the grid_problem) trains with dropout,
         the masks keyed per graph: distinct graph c of the step (ascending store id) is
@@ -827,9 +869,15 @@ class SiameseGCNTNMSE(object):
         else:
             _lib.embed(sg, gp.store_dev, nmax, gp.uniq, U, self.params, gp.emb, gp.status)
         eq, edb = (gp.emb, gp.emb) if gp.identity else (gp.emb[gp.q_pos], gp.emb[gp.db_pos])
-        _lib.score_grid_fwd_bwd(sg, eq, edb, gp.m, gp.n, self.params, gp.labels, gp.n,
-                                gp.m * gp.n, gp.y_stats, add_label_term, s_out, gp.n, gp.g_q,
-                                gp.g_db, self.grad, self.loss_buf, gp.ws_grid)
+        if self.is_dot:   # no variables in the head: the node-stack backward writes all of grad
+            E = int(gp.emb.shape[1])
+            _lib.dot_score_grid_fwd_bwd(sg, eq, E, edb, E, gp.m, gp.n, gp.labels, gp.n,
+                                        gp.m * gp.n, gp.y_stats, add_label_term, s_out, gp.n,
+                                        gp.g_q, gp.g_db, self.loss_buf, gp.ws_grid)
+        else:
+            _lib.score_grid_fwd_bwd(sg, eq, edb, gp.m, gp.n, self.params, gp.labels, gp.n,
+                                    gp.m * gp.n, gp.y_stats, add_label_term, s_out, gp.n, gp.g_q,
+                                    gp.g_db, self.grad, self.loss_buf, gp.ws_grid)
         if gp.identity:
             self.torch.add(gp.g_q, gp.g_db, out=gp.g_emb)
         else:
