@@ -287,6 +287,14 @@ def lib():
         L.sg_dot_score_grid_fwd_bwd.argtypes = [pm, vp, c_i64, vp, c_i64, c_i64, c_i64, vp, c_i64,
                                                 c_i64, vp, c_i32, vp, c_i64, vp, vp, vp, vp, vp]
         L.sg_dot_score_grid_fwd_bwd.restype = c_i32
+    # graph edit distance bounds over a grid of store graphs (include/siamese_ged.h); a
+    # library without them still loads
+    if all(hasattr(L, s) for s in GED_SYMBOLS):
+        L.sg_ged_grid_workspace_bytes.argtypes = [c_i64, c_i64, c_i32]
+        L.sg_ged_grid_workspace_bytes.restype = c_i64
+        L.sg_ged_grid.argtypes = [vp, vp, vp, c_i32, c_i32, vp, c_i64, vp, c_i64, c_i32, vp,
+                                  c_i64, vp, vp, vp, vp, vp]
+        L.sg_ged_grid.restype = c_i32
     _lib = L
     return L
 
@@ -352,6 +360,10 @@ EVAL_SYMBOLS = ('sg_eval_rows_workspace_bytes', 'sg_eval_rows')
 DOT_EMBED_SYMBOLS = ('sg_dot_score_grid', 'sg_dot_search_topk_workspace_bytes',
                      'sg_dot_search_topk', 'sg_dot_score_grid_bwd_workspace_bytes',
                      'sg_dot_score_grid_fwd_bwd')
+
+# the symbols of include/siamese_ged.h (graph edit distance on the device: the bipartite upper
+# bound and its certified lower bound for every pair of a grid; detected by presence)
+GED_SYMBOLS = ('sg_ged_grid_workspace_bytes', 'sg_ged_grid')
 
 # class_start entries of sg_pair_order_cls (include/siamese_hip.h SG_FAST_CLASSES_P1)
 FAST_CLASSES_P1 = 5
@@ -984,6 +996,36 @@ def eval_rows(scores, n_q, n_db, ld, true_rank, true_sim, ks, hits_out, best_ran
         _ptr(scores), int(n_q), int(n_db), int(ld), _ptr(true_rank), _ptr(true_sim), ks_arr,
         len(ks), _ptr(hits_out), _ptr(best_rank_out), _ptr(sqerr_out), _ptr(nan_out),
         _ptr(workspace), _stream(stream)), 'sg_eval_rows')
+
+
+def _ged_fn(name: str):
+    fn = getattr(lib(), name, None)
+    if fn is None or fn.argtypes is None:
+        raise SiameseHipError(name + ': this libsiamese_hip.so has no include/siamese_ged.h '
+                              'entry points')
+    return fn
+
+
+def ged_grid_workspace_bytes(n_q: int, n_db: int, n_max: int) -> int:
+    b = int(_ged_fn('sg_ged_grid_workspace_bytes')(int(n_q), int(n_db), int(n_max)))
+    if b < 0:
+        raise SiameseHipError('sg_ged_grid_workspace_bytes: the bipartite bounds serve stores '
+                              'of 1 <= n_max <= 32 and grids of at most 2^24 rows, 2^24 columns '
+                              'and 2^32 pairs')
+    return b
+
+
+def ged_grid(store_dev, n_max, q_idx, n_q, db_idx, n_db, both_orders, ub_out, ld, lb_out=None,
+             map_out=None, status=None, workspace=None, stream=None):
+    """sg_ged_grid over a device dense store (adj, types, n) = GraphStore.to_device(): the
+    bipartite upper bound ub_out int32 [n_q] rows of stride ld, and optionally the lower bound
+    lb_out (same shape) and the 1->2 assignment map_out int8 [n_q][n_db][n_max]; q_idx / db_idx
+    int32 device tensors or None (graphs 0 .. n_q-1 / 0 .. n_db-1)."""
+    adj, types, n = store_dev
+    check(_ged_fn('sg_ged_grid')(
+        _ptr(adj), _ptr(types), _ptr(n), int(n.numel()), int(n_max), _ptr(q_idx), int(n_q),
+        _ptr(db_idx), int(n_db), int(bool(both_orders)), _ptr(ub_out), int(ld), _ptr(lb_out),
+        _ptr(map_out), _ptr(status), _ptr(workspace), _stream(stream)), 'sg_ged_grid')
 
 
 def seed_advance(seed_dev, delta=1, stream=None):

@@ -87,7 +87,14 @@ class GraphSet:
 
 
 def load_graph_set(name: str = 'syn_aids700nef', n_max: int = 10, seed: int = 123,
-                   with_store: bool = True) -> GraphSet:
+                   with_store: bool = True, ged: str = 'synthetic', device='cuda') -> GraphSet:
+    """ged='synthetic': the seeded stand-in labels (data.synthetic_ged_matrix, the default);
+    ged='bp': the bipartite upper bounds of the graphs themselves, computed on `device`
+    (graphembedding_amd.ged.ged_matrix; needs the store)."""
+    if ged not in ('synthetic', 'bp'):
+        raise RuntimeError('Unknown ged labels {}'.format(ged))
+    if ged == 'bp' and not with_store:
+        raise RuntimeError("ged='bp' computes from the dense store: with_store=True is needed")
     tr, te = synthetic_graphs(name, seed)
     graphs = tr + te
     # sorted (not set-order) columns: identical encoding on every rank (quirk A7)
@@ -95,8 +102,13 @@ def load_graph_set(name: str = 'syn_aids700nef', n_max: int = 10, seed: int = 12
     mgs = [ModelGraph(g, enc) for g in graphs]
     # dense-slot store for the record paths; the graph-store path (web.py) builds CSR
     store = GraphStore(mgs, n_max, enc.input_dim()) if with_store else None
+    if ged == 'bp':
+        from .ged import ged_matrix
+        dmat = ged_matrix(store, device=device)
+    else:
+        dmat = synthetic_ged_matrix(graphs)
     return GraphSet(graphs=graphs, mgs=mgs, d_in=enc.input_dim(), n_max=n_max, store=store,
-                    ged=synthetic_ged_matrix(graphs))
+                    ged=dmat)
 
 
 class AllPairsShard(object):

@@ -73,6 +73,10 @@ DEFAULTS: Dict[str, Any] = dict(
     # sg_eval_rows launch per norm over the device matrix; needs test_path='embed' and
     # test_matrix='full')
     eval_path='host',
+    # ground-truth GED of the synthetic (syn_*) sets: 'synthetic' = the seeded stand-in matrix
+    # (data.synthetic_ged_matrix) | 'bp' = the bipartite upper bounds of the graphs themselves,
+    # computed on the device (ged.ged_matrix; graphs of at most 32 nodes)
+    ged_labels='synthetic',
     n_max=None,                # record node capacity (default: Padding max_in_dims or data max)
     record_dtype='f32',        # storage of Â in pair records: 'f32' | 'bf16' (config C3); fp32 math
     seed=123,                  # dropout RNG base seed (the reference's TF RNG was unseeded)

@@ -3,7 +3,9 @@
 Only `normalized_dist` (distance.py:59-60) is on the hot path.  `ged` and `mcs`
 shell out to the Java graph-matching-toolkit / the `chorus` library in the
 reference (distance.py:10-56); those solvers are out of scope here and raise
-unless a cached distance exists (see dist_calculator.DistCalculator).
+unless a cached distance exists (see dist_calculator.DistCalculator).  The one
+algorithm computed here is 'bp', the bipartite upper bound on the device
+(graphembedding_amd.ged, include/siamese_ged.h).
 """
 from __future__ import annotations
 
@@ -13,6 +15,15 @@ def normalized_dist(d, g1, g2):
 
 
 def ged(g1, g2, algo, debug=False, timeit=False):
+    """algo='bp': the bipartite (Riesen & Bunke) upper bound under the toolkit's AIDS cost
+    model, the smaller of both assignment orders (the reference's `_revtakemin` caches), for
+    graphs of at most 32 nodes.  The name is deliberately not 'hungarian': that the toolkit's
+    Hungarian mode builds the same cost matrix (node costs plus local degree differences) and
+    breaks ties the same way has not been checked, so its values are not claimed.  Every
+    other algo raises: exact A* and beam search are out of scope."""
+    if algo == 'bp':
+        from .ged import ged_pair
+        return ged_pair(g1, g2)[0]
     raise RuntimeError(
         'GED ground truth needs the external Java graph-matching-toolkit '
         '(reference src/distance.py:23-56); it is out of scope of this build. '

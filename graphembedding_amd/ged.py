@@ -1,0 +1,124 @@
+"""Graph edit distance on the device (include/siamese_ged.h): the bipartite approximation of
+Riesen & Bunke for every pair of a grid of store graphs in one call, with the certified lower
+bound of the same construction.
+
+Cost model (the graph-matching-toolkit's for the AIDS sets, doubled at alpha = 0.5): node
+insertion / deletion 1, node substitution 0 for equal `type` and 1 otherwise, edge insertion /
+deletion 1, edge substitution 0.  lb <= GED <= ub; where lb == ub the distance is exact.  The
+store serves graphs of at most 32 nodes (capacities 10 and 32).
+"""
+from __future__ import annotations
+
+import numpy as np
+
+from . import _lib
+
+GED_MAX_NODES = 32
+
+
+def _index(idx, device):
+    import torch
+    if idx is None:
+        return None
+    return torch.as_tensor(idx, dtype=torch.int32, device=device).reshape(-1).contiguous()
+
+
+def ged_grid(store, q_idx=None, db_idx=None, both_orders=True, bounds=False, mapping=False,
+             device='cuda', ld=None, return_status=False):
+    """Bipartite GED bounds of store graphs q_idx x db_idx (None: every graph of the store).
+
+    Returns the upper bound ub as a device int32 tensor [m][n] (min over both assignment
+    orders with both_orders); with bounds=True (ub, lb); with mapping=True additionally the
+    int8 tensor [m][n][n_max] of the 1->2 assignment (-1: deleted or beyond n1).  A graph id
+    outside the store or a node count outside [1, n_max] raises, unless return_status=True:
+    then the int32 device status tensor [1] is returned last and such entries read -1.
+    ld > n gives ub / lb as [m][:n] views of [m][ld] buffers."""
+    import torch
+    adj, types, n_nodes = store.to_device(device)
+    G = int(n_nodes.numel())
+    dev = adj.device
+    q, db = _index(q_idx, dev), _index(db_idx, dev)
+    m = G if q is None else int(q.numel())
+    n = G if db is None else int(db.numel())
+    ld = n if ld is None else int(ld)
+    if ld < n:
+        raise ValueError('ld {} below n {}'.format(ld, n))
+    nbytes = _lib.ged_grid_workspace_bytes(m, n, store.n_max)
+    ws = torch.empty(nbytes // 4 + 1, dtype=torch.int32, device=dev)
+    ub = torch.empty((m, ld), dtype=torch.int32, device=dev)
+    lb = torch.empty((m, ld), dtype=torch.int32, device=dev) if bounds else None
+    mp = torch.empty((m, n, store.n_max), dtype=torch.int8, device=dev) if mapping else None
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    _lib.ged_grid((adj, types, n_nodes), store.n_max, q, m, db, n, both_orders, ub, ld, lb, mp,
+                  status, ws)
+    if not return_status:
+        rc = int(status.item())
+        if rc != 0:
+            raise _lib.SiameseHipError('sg_ged_grid: {} (a graph id outside the store, or a '
+                                       'node count outside [1, n_max])'.format(
+                                           _lib._ERR_NAMES.get(rc, rc)))
+    out = [ub[:, :n]]
+    if bounds:
+        out.append(lb[:, :n])
+    if mapping:
+        out.append(mp)
+    if return_status:
+        out.append(status)
+    return out[0] if len(out) == 1 else tuple(out)
+
+
+class _ConstantEncoder(object):
+    """Graphs without the node feature: one type."""
+
+    def encode_columns(self, g):
+        return [0] * g.number_of_nodes()
+
+    def input_dim(self):
+        return 1
+
+
+def store_of_graphs(graphs, node_feat_name='type', n_max=None):
+    """A GraphStore of networkx graphs for the GED calls: types are the graphs' node_feat_name
+    values in sorted order (only their equality matters), n_max the largest node count unless
+    given."""
+    from .graphs import ModelGraph, NodeFeatureOneHotEncoder
+    from .packer import GraphStore
+    graphs = list(graphs)
+    if not graphs:
+        raise ValueError('no graphs')
+    have = [len(_attr(g, node_feat_name)) for g in graphs]
+    if all(h == g.number_of_nodes() for h, g in zip(have, graphs)):
+        enc = NodeFeatureOneHotEncoder(graphs, node_feat_name).pin_sorted()
+    elif not any(have):
+        enc = _ConstantEncoder()
+    else:
+        raise ValueError('some nodes have no {!r} attribute'.format(node_feat_name))
+    nm = max(g.number_of_nodes() for g in graphs)
+    n_max = max(nm, 1) if n_max is None else int(n_max)
+    if n_max > GED_MAX_NODES:
+        raise _lib.SiameseHipError('the bipartite GED bounds serve graphs of at most {} nodes '
+                                   '(largest here: {})'.format(GED_MAX_NODES, nm))
+    return GraphStore([ModelGraph(g, enc) for g in graphs], n_max, enc.input_dim())
+
+
+def _attr(g, name):
+    import networkx as nx
+    return nx.get_node_attributes(g, name)
+
+
+def ged_matrix(graphs_or_store, both_orders=True, device='cuda', node_feat_name='type'):
+    """All-pairs upper bounds as a host int64 matrix [G][G], ready for
+    DistCalculator.from_matrix.  With both_orders it is symmetric with a zero diagonal."""
+    store = graphs_or_store
+    if not hasattr(store, 'to_device'):
+        store = store_of_graphs(graphs_or_store, node_feat_name)
+    ub = ged_grid(store, both_orders=both_orders, device=device)
+    return ub.cpu().numpy().astype(np.int64)
+
+
+def ged_pair(g1, g2, device='cuda', node_feat_name='type'):
+    """(ub, lb) of two networkx graphs through a two-graph store, ub the min over both
+    assignment orders."""
+    store = store_of_graphs([g1, g2], node_feat_name)
+    ub, lb = ged_grid(store, [0], [1], both_orders=True, bounds=True, device=device)
+    return int(ub.item()), int(lb.item())

@@ -193,8 +193,14 @@ def main(flags=None, device='cuda', return_objects=False):
     if f.dataset.startswith('syn_'):
         gs = list(data.orig_train_graphs) + list(data.test_data.gs[i].nxgraph
                                                  for i in range(data.m))
-        dc = DistCalculator.from_matrix(f.dataset, gs, synthetic_ged_matrix(gs),
-                                        f.dist_metric, f.dist_algo)
+        if f.ged_labels == 'bp':   # structure-derived labels, computed on the device
+            from .ged import ged_matrix
+            dmat = ged_matrix(gs, device=device, node_feat_name=f.node_feat_name)
+        elif f.ged_labels == 'synthetic':
+            dmat = synthetic_ged_matrix(gs)
+        else:
+            raise RuntimeError('Unknown ged_labels {}'.format(f.ged_labels))
+        dc = DistCalculator.from_matrix(f.dataset, gs, dmat, f.dist_metric, f.dist_algo)
     else:
         dc = DistCalculator(f.dataset, f.dist_metric, f.dist_algo)
     model = create_model(f.model, data.input_dim(), f, device=device,
