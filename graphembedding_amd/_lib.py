@@ -295,6 +295,14 @@ def lib():
         L.sg_ged_grid.argtypes = [vp, vp, vp, c_i32, c_i32, vp, c_i64, vp, c_i64, c_i32, vp,
                                   c_i64, vp, vp, vp, vp, vp]
         L.sg_ged_grid.restype = c_i32
+    # exact graph edit distance under a budget (include/siamese_ged_exact.h); a library
+    # without it still loads
+    if all(hasattr(L, s) for s in GED_EXACT_SYMBOLS):
+        L.sg_ged_exact_grid_workspace_bytes.argtypes = [c_i64, c_i64, c_i32]
+        L.sg_ged_exact_grid_workspace_bytes.restype = c_i64
+        L.sg_ged_exact_grid.argtypes = [vp, vp, vp, c_i32, c_i32, vp, c_i64, vp, c_i64, c_i64,
+                                        vp, c_i64, vp, vp, vp, vp, vp, vp]
+        L.sg_ged_exact_grid.restype = c_i32
     _lib = L
     return L
 
@@ -364,6 +372,11 @@ DOT_EMBED_SYMBOLS = ('sg_dot_score_grid', 'sg_dot_search_topk_workspace_bytes',
 # the symbols of include/siamese_ged.h (graph edit distance on the device: the bipartite upper
 # bound and its certified lower bound for every pair of a grid; detected by presence)
 GED_SYMBOLS = ('sg_ged_grid_workspace_bytes', 'sg_ged_grid')
+
+# the symbols of include/siamese_ged_exact.h (exact graph edit distance under an expansion
+# budget: a branch and bound per pair seeded with the bipartite bounds; detected by presence)
+GED_EXACT_SYMBOLS = ('sg_ged_exact_grid_workspace_bytes', 'sg_ged_exact_grid')
+GED_EXACT_MAX_BUDGET = 1 << 24
 
 # class_start entries of sg_pair_order_cls (include/siamese_hip.h SG_FAST_CLASSES_P1)
 FAST_CLASSES_P1 = 5
@@ -1026,6 +1039,37 @@ def ged_grid(store_dev, n_max, q_idx, n_q, db_idx, n_db, both_orders, ub_out, ld
         _ptr(adj), _ptr(types), _ptr(n), int(n.numel()), int(n_max), _ptr(q_idx), int(n_q),
         _ptr(db_idx), int(n_db), int(bool(both_orders)), _ptr(ub_out), int(ld), _ptr(lb_out),
         _ptr(map_out), _ptr(status), _ptr(workspace), _stream(stream)), 'sg_ged_grid')
+
+
+def _ged_exact_fn(name: str):
+    fn = getattr(lib(), name, None)
+    if fn is None or fn.argtypes is None:
+        raise SiameseHipError(name + ': this libsiamese_hip.so has no '
+                              'include/siamese_ged_exact.h entry points')
+    return fn
+
+
+def ged_exact_grid_workspace_bytes(n_q: int, n_db: int, n_max: int) -> int:
+    b = int(_ged_exact_fn('sg_ged_exact_grid_workspace_bytes')(int(n_q), int(n_db), int(n_max)))
+    if b < 0:
+        raise SiameseHipError('sg_ged_exact_grid_workspace_bytes: the call serves stores of '
+                              '1 <= n_max <= 32 and grids of at most 2^24 rows, 2^24 columns '
+                              'and 2^32 pairs')
+    return b
+
+
+def ged_exact_grid(store_dev, n_max, q_idx, n_q, db_idx, n_db, max_expansions, ub_out, ld, lb_out,
+                   map_out=None, expansions_out=None, status=None, workspace=None, stream=None):
+    """sg_ged_exact_grid over a device dense store (adj, types, n) = GraphStore.to_device():
+    ub_out / lb_out int32 [n_q] rows of stride ld (lb == ub: proven), optionally the map of the
+    path that costs ub (int8 [n_q][n_db][n_max]) and the expansions spent (int64, stride ld);
+    q_idx / db_idx int32 device tensors or None."""
+    adj, types, n = store_dev
+    check(_ged_exact_fn('sg_ged_exact_grid')(
+        _ptr(adj), _ptr(types), _ptr(n), int(n.numel()), int(n_max), _ptr(q_idx), int(n_q),
+        _ptr(db_idx), int(n_db), int(max_expansions), _ptr(ub_out), int(ld), _ptr(lb_out),
+        _ptr(map_out), _ptr(expansions_out), _ptr(status), _ptr(workspace), _stream(stream)),
+        'sg_ged_exact_grid')
 
 
 def seed_advance(seed_dev, delta=1, stream=None):

@@ -90,11 +90,14 @@ def load_graph_set(name: str = 'syn_aids700nef', n_max: int = 10, seed: int = 12
                    with_store: bool = True, ged: str = 'synthetic', device='cuda') -> GraphSet:
     """ged='synthetic': the seeded stand-in labels (data.synthetic_ged_matrix, the default);
     ged='bp': the bipartite upper bounds of the graphs themselves, computed on `device`
-    (graphembedding_amd.ged.ged_matrix; needs the store)."""
-    if ged not in ('synthetic', 'bp'):
+    (graphembedding_amd.ged.ged_matrix; needs the store); ged='exact': the budgeted branch and
+    bound's ub at ged.GED_EXACT_DEFAULT_BUDGET expansions per pair, the exact distance wherever
+    it is proven (the count of unproven pairs is logged)."""
+    if ged not in ('synthetic', 'bp', 'exact'):
         raise RuntimeError('Unknown ged labels {}'.format(ged))
-    if ged == 'bp' and not with_store:
-        raise RuntimeError("ged='bp' computes from the dense store: with_store=True is needed")
+    if ged in ('bp', 'exact') and not with_store:
+        raise RuntimeError("ged={!r} computes from the dense store: with_store=True is "
+                           "needed".format(ged))
     tr, te = synthetic_graphs(name, seed)
     graphs = tr + te
     # sorted (not set-order) columns: identical encoding on every rank (quirk A7)
@@ -105,6 +108,9 @@ def load_graph_set(name: str = 'syn_aids700nef', n_max: int = 10, seed: int = 12
     if ged == 'bp':
         from .ged import ged_matrix
         dmat = ged_matrix(store, device=device)
+    elif ged == 'exact':
+        from .ged import exact_label_matrix
+        dmat = exact_label_matrix(store, device=device)
     else:
         dmat = synthetic_ged_matrix(graphs)
     return GraphSet(graphs=graphs, mgs=mgs, d_in=enc.input_dim(), n_max=n_max, store=store,

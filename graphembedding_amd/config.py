@@ -75,7 +75,9 @@ DEFAULTS: Dict[str, Any] = dict(
     eval_path='host',
     # ground-truth GED of the synthetic (syn_*) sets: 'synthetic' = the seeded stand-in matrix
     # (data.synthetic_ged_matrix) | 'bp' = the bipartite upper bounds of the graphs themselves,
-    # computed on the device (ged.ged_matrix; graphs of at most 32 nodes)
+    # computed on the device (ged.ged_matrix; graphs of at most 32 nodes) | 'exact' = the
+    # budgeted branch and bound seeded with them (ged.exact_label_matrix): the exact distance
+    # wherever it is proven (graphs of at most about 10 nodes), its best ub elsewhere
     ged_labels='synthetic',
     n_max=None,                # record node capacity (default: Padding max_in_dims or data max)
     record_dtype='f32',        # storage of Â in pair records: 'f32' | 'bf16' (config C3); fp32 math

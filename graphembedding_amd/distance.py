@@ -3,9 +3,10 @@
 Only `normalized_dist` (distance.py:59-60) is on the hot path.  `ged` and `mcs`
 shell out to the Java graph-matching-toolkit / the `chorus` library in the
 reference (distance.py:10-56); those solvers are out of scope here and raise
-unless a cached distance exists (see dist_calculator.DistCalculator).  The one
-algorithm computed here is 'bp', the bipartite upper bound on the device
-(graphembedding_amd.ged, include/siamese_ged.h).
+unless a cached distance exists (see dist_calculator.DistCalculator).  Two
+algorithms are computed here, on the device (graphembedding_amd.ged): 'bp', the
+bipartite upper bound (include/siamese_ged.h), and 'exact', the budgeted branch
+and bound seeded with it (include/siamese_ged_exact.h).
 """
 from __future__ import annotations
 
@@ -19,11 +20,24 @@ def ged(g1, g2, algo, debug=False, timeit=False):
     model, the smaller of both assignment orders (the reference's `_revtakemin` caches), for
     graphs of at most 32 nodes.  The name is deliberately not 'hungarian': that the toolkit's
     Hungarian mode builds the same cost matrix (node costs plus local degree differences) and
-    breaks ties the same way has not been checked, so its values are not claimed.  Every
-    other algo raises: exact A* and beam search are out of scope."""
+    breaks ties the same way has not been checked, so its values are not claimed.
+
+    algo='exact': the exact distance under the same cost model, proven by the budgeted branch
+    and bound within ged.GED_EXACT_DEFAULT_BUDGET = 2^20 expansions; a pair it cannot prove
+    (more than 16 nodes, or the budget spent) raises with the bounds it has.  The name is not
+    'astar': the value is the same distance, the program is not the toolkit's.
+
+    Every other algo raises: the toolkit's A* and beam search are out of scope."""
     if algo == 'bp':
         from .ged import ged_pair
         return ged_pair(g1, g2)[0]
+    if algo == 'exact':
+        from .ged import GED_EXACT_DEFAULT_BUDGET, ged_pair
+        ub, lb = ged_pair(g1, g2, exact_budget=GED_EXACT_DEFAULT_BUDGET)
+        if ub != lb:
+            raise RuntimeError('exact GED not proven within {} expansions: ub {} lb {}'.format(
+                GED_EXACT_DEFAULT_BUDGET, ub, lb))
+        return ub
     raise RuntimeError(
         'GED ground truth needs the external Java graph-matching-toolkit '
         '(reference src/distance.py:23-56); it is out of scope of this build. '

@@ -6,6 +6,11 @@ Cost model (the graph-matching-toolkit's for the AIDS sets, doubled at alpha = 0
 insertion / deletion 1, node substitution 0 for equal `type` and 1 otherwise, edge insertion /
 deletion 1, edge substitution 0.  lb <= GED <= ub; where lb == ub the distance is exact.  The
 store serves graphs of at most 32 nodes (capacities 10 and 32).
+
+With exact_budget the calls go through include/siamese_ged_exact.h instead: a depth-first branch
+and bound per pair, seeded with those bounds and cut off after exact_budget expansions.  It
+proves the distance (lb == ub) where it finishes, which it does on graphs of at most about 10
+nodes, and tightens ub elsewhere; graphs of more than 16 nodes keep the bipartite bounds.
 """
 from __future__ import annotations
 
@@ -14,6 +19,8 @@ import numpy as np
 from . import _lib
 
 GED_MAX_NODES = 32
+GED_EXACT_MAX_NODES = 16             # larger graphs keep the bipartite bounds
+GED_EXACT_DEFAULT_BUDGET = 1 << 20   # expansions per pair of distance.ged(..., 'exact')
 
 
 def _index(idx, device):
@@ -24,7 +31,7 @@ def _index(idx, device):
 
 
 def ged_grid(store, q_idx=None, db_idx=None, both_orders=True, bounds=False, mapping=False,
-             device='cuda', ld=None, return_status=False):
+             device='cuda', ld=None, return_status=False, exact_budget=None, expansions=False):
     """Bipartite GED bounds of store graphs q_idx x db_idx (None: every graph of the store).
 
     Returns the upper bound ub as a device int32 tensor [m][n] (min over both assignment
@@ -32,8 +39,18 @@ def ged_grid(store, q_idx=None, db_idx=None, both_orders=True, bounds=False, map
     int8 tensor [m][n][n_max] of the 1->2 assignment (-1: deleted or beyond n1).  A graph id
     outside the store or a node count outside [1, n_max] raises, unless return_status=True:
     then the int32 device status tensor [1] is returned last and such entries read -1.
-    ld > n gives ub / lb as [m][:n] views of [m][ld] buffers."""
+    ld > n gives ub / lb as [m][:n] views of [m][ld] buffers.
+
+    exact_budget=B (an int in [0, 2^24]) runs the budgeted branch and bound on every pair: ub is
+    the cost of the best edit path found (never above the bipartite one), lb equals ub where the
+    distance is proven, the mapping is that path's, and expansions=True additionally returns the
+    int64 tensor [m][n] of expansions spent (after the mapping, before the status)."""
     import torch
+    exact = exact_budget is not None
+    if expansions and not exact:
+        raise ValueError('expansions are counted by the exact search: pass exact_budget')
+    if exact and not both_orders:
+        raise ValueError('the exact search is seeded with both assignment orders')
     adj, types, n_nodes = store.to_device(device)
     G = int(n_nodes.numel())
     dev = adj.device
@@ -43,25 +60,34 @@ def ged_grid(store, q_idx=None, db_idx=None, both_orders=True, bounds=False, map
     ld = n if ld is None else int(ld)
     if ld < n:
         raise ValueError('ld {} below n {}'.format(ld, n))
-    nbytes = _lib.ged_grid_workspace_bytes(m, n, store.n_max)
+    nbytes = (_lib.ged_exact_grid_workspace_bytes if exact else
+              _lib.ged_grid_workspace_bytes)(m, n, store.n_max)
     ws = torch.empty(nbytes // 4 + 1, dtype=torch.int32, device=dev)
     ub = torch.empty((m, ld), dtype=torch.int32, device=dev)
-    lb = torch.empty((m, ld), dtype=torch.int32, device=dev) if bounds else None
+    lb = torch.empty((m, ld), dtype=torch.int32, device=dev) if bounds or exact else None
     mp = torch.empty((m, n, store.n_max), dtype=torch.int8, device=dev) if mapping else None
+    ex = torch.empty((m, ld), dtype=torch.int64, device=dev) if expansions else None
     status = torch.zeros(1, dtype=torch.int32, device=dev)
-    _lib.ged_grid((adj, types, n_nodes), store.n_max, q, m, db, n, both_orders, ub, ld, lb, mp,
-                  status, ws)
+    if exact:
+        _lib.ged_exact_grid((adj, types, n_nodes), store.n_max, q, m, db, n, int(exact_budget),
+                            ub, ld, lb, mp, ex, status, ws)
+    else:
+        _lib.ged_grid((adj, types, n_nodes), store.n_max, q, m, db, n, both_orders, ub, ld, lb,
+                      mp, status, ws)
     if not return_status:
         rc = int(status.item())
         if rc != 0:
-            raise _lib.SiameseHipError('sg_ged_grid: {} (a graph id outside the store, or a '
+            raise _lib.SiameseHipError('{}: {} (a graph id outside the store, or a '
                                        'node count outside [1, n_max])'.format(
+                                           'sg_ged_exact_grid' if exact else 'sg_ged_grid',
                                            _lib._ERR_NAMES.get(rc, rc)))
     out = [ub[:, :n]]
     if bounds:
         out.append(lb[:, :n])
     if mapping:
         out.append(mp)
+    if expansions:
+        out.append(ex[:, :n])
     if return_status:
         out.append(status)
     return out[0] if len(out) == 1 else tuple(out)
@@ -106,19 +132,42 @@ def _attr(g, name):
     return nx.get_node_attributes(g, name)
 
 
-def ged_matrix(graphs_or_store, both_orders=True, device='cuda', node_feat_name='type'):
+def ged_matrix(graphs_or_store, both_orders=True, device='cuda', node_feat_name='type',
+               exact_budget=None):
     """All-pairs upper bounds as a host int64 matrix [G][G], ready for
-    DistCalculator.from_matrix.  With both_orders it is symmetric with a zero diagonal."""
+    DistCalculator.from_matrix.  With both_orders it is symmetric with a zero diagonal.
+    With exact_budget=B: (matrix, proven), the budgeted search's ub and the bool matrix of the
+    pairs whose distance it proved (ub is the exact distance there)."""
     store = graphs_or_store
     if not hasattr(store, 'to_device'):
         store = store_of_graphs(graphs_or_store, node_feat_name)
+    if exact_budget is not None:
+        ub, lb = ged_grid(store, both_orders=both_orders, bounds=True, device=device,
+                          exact_budget=exact_budget)
+        ub, lb = ub.cpu().numpy().astype(np.int64), lb.cpu().numpy().astype(np.int64)
+        return ub, ub == lb
     ub = ged_grid(store, both_orders=both_orders, device=device)
     return ub.cpu().numpy().astype(np.int64)
 
 
-def ged_pair(g1, g2, device='cuda', node_feat_name='type'):
+def ged_pair(g1, g2, device='cuda', node_feat_name='type', exact_budget=None):
     """(ub, lb) of two networkx graphs through a two-graph store, ub the min over both
-    assignment orders."""
+    assignment orders; with exact_budget=B those of the budgeted search (ub == lb: proven)."""
     store = store_of_graphs([g1, g2], node_feat_name)
-    ub, lb = ged_grid(store, [0], [1], both_orders=True, bounds=True, device=device)
+    ub, lb = ged_grid(store, [0], [1], both_orders=True, bounds=True, device=device,
+                      exact_budget=exact_budget)
     return int(ub.item()), int(lb.item())
+
+
+def exact_label_matrix(graphs_or_store, device='cuda', node_feat_name='type',
+                       budget=GED_EXACT_DEFAULT_BUDGET):
+    """The label matrix of ged='exact' / ged_labels='exact': the budgeted search's ub for all
+    pairs, with the number of pairs left unproven logged (their ub is the best path found, as
+    the reference's AIDS10k labels are a minimum over approximate solvers)."""
+    import logging
+    dmat, proven = ged_matrix(graphs_or_store, device=device, node_feat_name=node_feat_name,
+                              exact_budget=budget)
+    logging.getLogger(__name__).info(
+        'exact GED labels: %d of %d pairs left unproven within %d expansions',
+        int((~proven).sum()), proven.size, budget)
+    return dmat

@@ -196,6 +196,9 @@ def main(flags=None, device='cuda', return_objects=False):
         if f.ged_labels == 'bp':   # structure-derived labels, computed on the device
             from .ged import ged_matrix
             dmat = ged_matrix(gs, device=device, node_feat_name=f.node_feat_name)
+        elif f.ged_labels == 'exact':   # the budgeted exact search; ub where unproven
+            from .ged import exact_label_matrix
+            dmat = exact_label_matrix(gs, device=device, node_feat_name=f.node_feat_name)
         elif f.ged_labels == 'synthetic':
             dmat = synthetic_ged_matrix(gs)
         else:
