@@ -6,6 +6,7 @@ be loaded this module raises, loudly, on first use.
 from __future__ import annotations
 
 import ctypes
+import functools
 import os
 from typing import List, Optional
 
@@ -855,12 +856,20 @@ _NO_WEB_DROP = ('embed-once training with graph-keyed dropout serves models on t
                 'path whose stack fits the LDS')
 
 
-def _web_drop_fn(name: str):
+def _optional_fn(name: str, header: str):
+    """The entry point `name` of a header that an older library may lack, or an error."""
     fn = getattr(lib(), name, None)
     if fn is None or fn.argtypes is None:
-        raise SiameseHipError(name + ': this libsiamese_hip.so has no '
-                              'include/siamese_web_embed_drop.h entry points')
+        raise SiameseHipError('{}: this libsiamese_hip.so has no include/{} entry '
+                              'points'.format(name, header))
     return fn
+
+
+_web_drop_fn = functools.partial(_optional_fn, header='siamese_web_embed_drop.h')
+_dot_fn = functools.partial(_optional_fn, header='siamese_dot_embed.h')
+_eval_fn = functools.partial(_optional_fn, header='siamese_eval.h')
+_ged_fn = functools.partial(_optional_fn, header='siamese_ged.h')
+_ged_exact_fn = functools.partial(_optional_fn, header='siamese_ged_exact.h')
 
 
 def web_embed_drop_workspace_bytes(m: SgModel, count: int) -> int:
@@ -924,14 +933,6 @@ _NO_DOT = ('the Dot grid serves models whose pair head is Dot, off the graph-sto
            'an embedding of at most 512 floats')
 
 
-def _dot_fn(name: str):
-    fn = getattr(lib(), name, None)
-    if fn is None or fn.argtypes is None:
-        raise SiameseHipError(name + ': this libsiamese_hip.so has no '
-                              'include/siamese_dot_embed.h entry points')
-    return fn
-
-
 def dot_score_grid(m: SgModel, emb_q, ld_q, emb_db, ld_db, n_q, n_db, apply_final, out, ld_out,
                    stream=None):
     """sg_dot_score_grid: out[i][j] = Σ_a emb_q[i][a] · emb_db[j][a] (final activation applied
@@ -981,14 +982,6 @@ def dot_score_grid_fwd_bwd(m: SgModel, emb_q, ld_q, emb_db, ld_db, n_q, n_db, la
         _ptr(loss_out), _ptr(workspace), _stream(stream)), 'sg_dot_score_grid_fwd_bwd')
 
 
-def _eval_fn(name: str):
-    fn = getattr(lib(), name, None)
-    if fn is None or fn.argtypes is None:
-        raise SiameseHipError(name + ': this libsiamese_hip.so has no include/siamese_eval.h '
-                              'entry points')
-    return fn
-
-
 def eval_workspace_bytes(n_q: int, n_db: int, n_ks: int) -> int:
     b = int(_eval_fn('sg_eval_rows_workspace_bytes')(int(n_q), int(n_db), int(n_ks)))
     if b < 0:
@@ -1011,14 +1004,6 @@ def eval_rows(scores, n_q, n_db, ld, true_rank, true_sim, ks, hits_out, best_ran
         _ptr(workspace), _stream(stream)), 'sg_eval_rows')
 
 
-def _ged_fn(name: str):
-    fn = getattr(lib(), name, None)
-    if fn is None or fn.argtypes is None:
-        raise SiameseHipError(name + ': this libsiamese_hip.so has no include/siamese_ged.h '
-                              'entry points')
-    return fn
-
-
 def ged_grid_workspace_bytes(n_q: int, n_db: int, n_max: int) -> int:
     b = int(_ged_fn('sg_ged_grid_workspace_bytes')(int(n_q), int(n_db), int(n_max)))
     if b < 0:
@@ -1039,14 +1024,6 @@ def ged_grid(store_dev, n_max, q_idx, n_q, db_idx, n_db, both_orders, ub_out, ld
         _ptr(adj), _ptr(types), _ptr(n), int(n.numel()), int(n_max), _ptr(q_idx), int(n_q),
         _ptr(db_idx), int(n_db), int(bool(both_orders)), _ptr(ub_out), int(ld), _ptr(lb_out),
         _ptr(map_out), _ptr(status), _ptr(workspace), _stream(stream)), 'sg_ged_grid')
-
-
-def _ged_exact_fn(name: str):
-    fn = getattr(lib(), name, None)
-    if fn is None or fn.argtypes is None:
-        raise SiameseHipError(name + ': this libsiamese_hip.so has no '
-                              'include/siamese_ged_exact.h entry points')
-    return fn
 
 
 def ged_exact_grid_workspace_bytes(n_q: int, n_db: int, n_max: int) -> int:

@@ -160,15 +160,21 @@ class AllPairsGrid(object):
     backward per graph instead of G² pair bodies (include/siamese_embed_train.h).  Same
     loss and gradient as AllPairsShard's batch at dropout 0, up to fp32 summation order."""
 
+    # the model's methods a step goes through (web.WebAllPairsGrid: their web_* counterparts)
+    API = 'grid_'
+
     def __init__(self, gs: GraphSet, labels: np.ndarray, device='cuda', dropout=None):
+        self._setup(gs.store, labels, device, dropout)
+
+    def _setup(self, store, labels, device, dropout):
         import torch
-        G = len(gs.graphs)
+        G = len(store)
         lab = np.ascontiguousarray(np.asarray(labels, np.float32).reshape(G, G))
-        self.store = gs.store
+        self.store = store
         self.total = G * G
         self.labels = torch.from_numpy(lab).to(device)
         y = lab.reshape(-1).astype(np.float64)
-        ybar = y.mean()
+        ybar = y.mean() if y.size else 0.0
         self.y_stats = torch.tensor([ybar, 0.5 * ((y - ybar) ** 2).sum()], dtype=torch.float32,
                                     device=device)
         self.dropout = dropout
@@ -179,17 +185,17 @@ class AllPairsGrid(object):
         """The model's GridProblem of this grid (built once per model)."""
         owner = self._owner() if self._owner is not None else None
         if owner is not model:
-            self._problem = model.grid_problem(self.store, self.labels, y_stats=self.y_stats,
-                                               dropout=self.dropout)
+            self._problem = getattr(model, self.API + 'problem')(
+                self.store, self.labels, y_stats=self.y_stats, dropout=self.dropout)
             self._owner = weakref.ref(model)
         return self._problem
 
     def fwd_bwd(self, model, add_label_term: bool = True):
         """Leaves the gradient / loss_mse in model.grad / model.loss_buf."""
-        model.grid_fwd_bwd(self.problem(model), add_label_term=add_label_term)
+        getattr(model, self.API + 'fwd_bwd')(self.problem(model), add_label_term=add_label_term)
 
     def train_step(self, model, sync: bool = True):
-        return model.grid_train_step(self.problem(model), sync=sync)
+        return getattr(model, self.API + 'train_step')(self.problem(model), sync=sync)
 
 
 class AllPairsStream(object):

@@ -14,7 +14,7 @@ SOURCES = ['siamese_hip.hip', 'sg_generic.hip', 'sg_fast.hip', 'sg_fast_att.hip'
            'sg_eval.hip', 'sg_dot_grid.hip', 'sg_ged.hip', 'sg_ged_exact.hip']
 HEADERS = ['sg_common.h', 'sg_plan.h', 'sg_paths.h', 'sg_mfma.h', 'sg_gen_nodes.h',
            'sg_embed_plan.h', 'sg_embed_bwd.h', 'sg_web_grid.h', 'sg_search_lists.h',
-           'sg_ged_common.h']
+           'sg_search_split.h', 'sg_ged_common.h']
 # MI355X only: the kernels use gfx950's 160 KB LDS (web_wgrad_kernel_b3 holds ≈66.6 KB),
 # its MFMA shapes and wave64 layouts; there is no other target
 ARCH = 'gfx950'

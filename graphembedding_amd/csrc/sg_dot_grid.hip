@@ -16,8 +16,6 @@ namespace {
 using sgk::f4;
 
 constexpr int kDotMaxE = 512;
-constexpr int64_t kDotSegMin = 1024;    // the library's own segment choice lies in
-constexpr int64_t kDotSegMax = 65536;   // [kDotSegMin, kDotSegMax] columns
 constexpr int kDotListLds = 32768;      // LDS for the lists of a workgroup's queries
 constexpr int kTileLd = 68;             // floats per row of a wavefront's 16 x 64 score tile:
                                         // rows 4 g + r of the four lane groups 16 banks apart
@@ -130,16 +128,14 @@ __global__ void __launch_bounds__(256) dot_grid_kernel(DotGridArgs A) {
 }
 
 // ---------------------------------------------------------------------------
-// Search.  How a call is cut: S segments of seg database columns times nqc chunks of qb
-// queries (a multiple of 16), one workgroup each; wavefront w of a workgroup takes the
-// chunk's groups of 16 queries w, w + nw, …  For each 64-column block of the segment it
-// computes the group's 16 x 64 scores (dot_tile), turns them through its own LDS tile so that
+// Search.  How a call is cut (search_split, sg_search_split.h): S segments of seg database
+// columns times nqc chunks of qb queries (a multiple of 16), one workgroup each; wavefront w of
+// a workgroup takes the chunk's groups of 16 queries w, w + nw, …  For each 64-column block of
+// the segment it computes the group's 16 x 64 scores (dot_tile), turns them through its own LDS tile so that
 // lane l holds column j0 + l of one query, and meets that query's running list exactly as
 // sg_search_kernel does (list_insert).  A query's list belongs to one wavefront: no barrier.
 // ---------------------------------------------------------------------------
-struct DotSearchPlan {
-  int64_t seg, nseg, nqc, qb, blocks;
-  int64_t cand, ws_bytes;   // cand: candidate entries, nseg · m · k
+struct DotSearchPlan : SearchSplit {   // the workspace is the candidates alone: cand_bytes
   int waves;
   size_t lds;
 };
@@ -148,44 +144,13 @@ struct DotSearchPlan {
 int dot_search_plan(const sg_model_t *model, int64_t m, int64_t n, int32_t k, int64_t seg_cols,
                     SgGenPlan *P, DotSearchPlan *S) {
   if (!model || m < 0 || n < 0) return SG_ERR_ARG;
-  const int rc = dot_plan(model, P);
+  int rc = dot_plan(model, P);
   if (rc != SG_OK) return rc;
-  if (k < 1) return SG_ERR_ARG;
-  if (k > kTopkMax) return SG_ERR_UNSUPPORTED;
-  if (k > n) return SG_ERR_ARG;
-  if (seg_cols < 0 || (seg_cols & 63) != 0) return SG_ERR_ARG;
-  if (m > kMaxRows || n > kMaxRows) return SG_ERR_UNSUPPORTED;   // n < 2^31 with it
-  const int64_t target = (int64_t)sg_num_cus() * 8;   // workgroups that fill the device
-  const int64_t max_qc = m > 16 ? (m + 15) / 16 : 1;
-  int64_t seg = seg_cols;
-  if (seg == 0) {
-    // as search_plan (sg_search.hip): segments of 1024 columns per list entry (at least 4096)
-    // amortise the insertions and the merge, shorter ones only where the queries alone cannot
-    // fill the device
-    seg = 4096;
-    while (seg < 1024 * (int64_t)k) seg <<= 1;   // k <= 64: at most kDotSegMax
-    while (seg > kDotSegMin && ((n + seg - 1) / seg) * max_qc < target) seg >>= 1;
-  }
-  if (seg > n) seg = (n + 63) & ~(int64_t)63;   // one segment (k <= n: n >= 1)
-  S->seg = seg;
-  S->nseg = (n + seg - 1) / seg;
-  int64_t nqc = (target + S->nseg - 1) / S->nseg;
-  nqc = nqc > max_qc ? max_qc : nqc;
-  int64_t qb = (((m + nqc - 1) / nqc) + 15) & ~(int64_t)15;
-  const int64_t qb_cap = (kDotListLds / (kListBytes * k)) & ~15;   // >= 32
-  qb = qb > qb_cap ? qb_cap : qb;
-  qb = qb < 16 ? 16 : qb;
-  S->qb = qb;
-  S->nqc = m > 0 ? (m + qb - 1) / qb : 1;
-  S->blocks = S->nseg * S->nqc;
-  if (S->blocks > 0x7FFFFFFF) return SG_ERR_UNSUPPORTED;
-  S->waves = qb / 16 > 4 ? 4 : (int)(qb / 16);
-  S->lds = (size_t)qb * k * kListBytes + (size_t)S->waves * kTileFloats * 4;
-  S->cand = S->nseg * m * k;
-  // the library's own choice depends on m and on the device: its workspace is sized for the
-  // shortest segments it may pick, so the size is monotone and the same everywhere
-  const int64_t ws_seg = seg_cols == 0 ? (n + kDotSegMin - 1) / kDotSegMin : S->nseg;
-  S->ws_bytes = ws_seg * m * k * kListBytes + 256;
+  // 8 workgroups per CU fill the device
+  rc = search_split(SearchUnit{(int64_t)sg_num_cus() * 8, 16, kDotListLds}, m, n, k, seg_cols, S);
+  if (rc != SG_OK) return rc;
+  S->waves = S->qb / 16 > 4 ? 4 : (int)(S->qb / 16);
+  S->lds = (size_t)S->qb * k * kListBytes + (size_t)S->waves * kTileFloats * 4;
   return SG_OK;
 }
 
@@ -194,10 +159,7 @@ struct DotSearchArgs {
   int64_t seg, nseg;
   int qb, k, apply_final, largest, final_act;
   float yeta;
-  uint64_t *ckey;   // candidates [nseg][m][k], or
-  float *cval;
-  int32_t *idx;     // with one segment the results themselves [m][k]
-  float *val;       // (may be null)
+  ListOut out;
 };
 
 __global__ void __launch_bounds__(256) dot_search_kernel(DotSearchArgs A) {
@@ -213,8 +175,7 @@ __global__ void __launch_bounds__(256) dot_search_kernel(DotSearchArgs A) {
   float *lvals = (float *)(lkeys + (size_t)A.qb * k);           // [qb][k]
   float *tile = lvals + (size_t)A.qb * k + wave * kTileFloats;   // [16][kTileLd], this wave's
   for (int64_t i0 = q0 + 16 * wave; i0 < q1; i0 += 16 * nw)
-    for (int R = 0; R < 16 && i0 + R < q1; ++R)
-      if (lane < k) lkeys[(i0 + R - q0) * k + lane] = ~0ull;
+    for (int R = 0; R < 16 && i0 + R < q1; ++R) list_reset(lkeys + (i0 + R - q0) * k, k, lane);
   sg_wsync();
   for (int64_t i0 = q0 + 16 * wave; i0 < q1; i0 += 16 * nw) {
     for (int64_t j0 = c0; j0 < c1; j0 += 64) {
@@ -232,11 +193,7 @@ __global__ void __launch_bounds__(256) dot_search_kernel(DotSearchArgs A) {
         uint64_t *lk = lkeys + (i0 + R - q0) * k;
         const uint64_t thr = lk[k - 1];
         const uint64_t key = jst < A.O.n ? topk_key(s, (uint32_t)jst, A.largest) : ~0ull;
-        const uint64_t hits = __ballot(key < thr);
-        if (hits) {
-          list_insert(lk, lvals + (i0 + R - q0) * k, k, lane, key, s, hits, thr);
-          sg_wsync();
-        }
+        list_offer(lk, lvals + (i0 + R - q0) * k, k, lane, key, s, thr);
       }
       sg_wsync();   // the next block overwrites the tile
     }
@@ -248,12 +205,12 @@ __global__ void __launch_bounds__(256) dot_search_kernel(DotSearchArgs A) {
       const uint64_t key = lkeys[(i - q0) * k + lane];
       const float val = lvals[(i - q0) * k + lane];
       if (A.nseg == 1) {   // k <= n: every entry is a column
-        A.idx[i * k + lane] = (int32_t)(uint32_t)key;
-        if (A.val) A.val[i * k + lane] = val;
+        A.out.idx[i * k + lane] = (int32_t)(uint32_t)key;
+        if (A.out.val) A.out.val[i * k + lane] = val;
       } else {   // a short last segment leaves sentinels; their values are never read
         const int64_t o = (sgm * A.O.m + i) * k + lane;
-        A.ckey[o] = key;
-        A.cval[o] = val;
+        A.out.ckey[o] = key;
+        A.out.cval[o] = val;
       }
     }
 }
@@ -427,12 +384,7 @@ __global__ void __launch_bounds__(256) dot_loss_kernel(const float *__restrict__
 // the model checks of the training call: dot_plan, then no effective dropout (train_plan's rule)
 int dot_train_plan(const sg_model_t *model, SgGenPlan *P) {
   const int rc = dot_plan(model, P);
-  if (rc != SG_OK) return rc;
-  if (!(model->keep_prob > 0.f && model->keep_prob <= 1.f)) return SG_ERR_ARG;
-  if (sg_keep_threshold(model->keep_prob) != 65536u)
-    for (int li = 0; li < model->num_layers; ++li)
-      if (model->layers[li].dropout) return SG_ERR_UNSUPPORTED;
-  return SG_OK;
+  return rc != SG_OK ? rc : plan_no_dropout(model);
 }
 
 void dot_adj_launch(const float *G, int64_t rs, int64_t ks, int64_t R, int64_t K, const float *X,
@@ -492,7 +444,7 @@ int64_t sg_dot_search_topk_workspace_bytes(const sg_model_t *model, int64_t m, i
   SgGenPlan P;
   DotSearchPlan S;
   if (dot_search_plan(model, m, n, k, seg_cols, &P, &S) != SG_OK) return -1;
-  return S.ws_bytes;
+  return S.cand_bytes;
 }
 
 int32_t sg_dot_search_topk(const sg_model_t *model, const float *emb_q, int64_t ld_q,
@@ -520,16 +472,11 @@ int32_t sg_dot_search_topk(const sg_model_t *model, const float *emb_q, int64_t 
   A.largest = largest ? 1 : 0;
   A.final_act = P.final_act;
   A.yeta = P.yeta;
-  A.ckey = (uint64_t *)workspace;
-  A.cval = (float *)(A.ckey + S.cand);
-  A.idx = idx_out;
-  A.val = val_out;
+  A.out = list_out(workspace, S, idx_out, val_out);
   (void)hipGetLastError();   // report only this call's launch errors
   hipLaunchKernelGGL(dot_search_kernel, dim3((unsigned)S.blocks), dim3(64 * S.waves), S.lds, st,
                      A);
-  if (S.nseg > 1)
-    hipLaunchKernelGGL(sg_search_merge_kernel, dim3((unsigned)m), dim3(64), 0, st, A.ckey,
-                       A.cval, m, (int)S.nseg, (int)k, idx_out, val_out);
+  launch_search_merge(A.out, S, m, k, st);
   return hipGetLastError() == hipSuccess ? SG_OK : SG_ERR_HIP;
 }
 

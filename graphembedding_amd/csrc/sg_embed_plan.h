@@ -52,17 +52,22 @@ int grid_plan(const sg_model_t *model, SgGenPlan *P) {
   return SG_OK;
 }
 
-// grid_plan / embed_plan of a model without any effective dropout, or an SG_ERR_* code
-// (embed-once training, include/siamese_embed_train.h)
-int train_plan(const sg_model_t *model, SgGenPlan *P, bool grid) {
-  if (!model) return SG_ERR_ARG;
-  const int rc = grid ? grid_plan(model, P) : embed_plan(model, P);
-  if (rc != SG_OK) return rc;
+// SG_OK for a model without any effective dropout (what embed-once training without masks
+// serves: train_plan, and dot_train_plan of sg_dot_grid.hip), or an SG_ERR_* code
+int plan_no_dropout(const sg_model_t *model) {
   if (!(model->keep_prob > 0.f && model->keep_prob <= 1.f)) return SG_ERR_ARG;
   if (sg_keep_threshold(model->keep_prob) != 65536u)
     for (int li = 0; li < model->num_layers; ++li)
       if (model->layers[li].dropout) return SG_ERR_UNSUPPORTED;
   return SG_OK;
+}
+
+// grid_plan / embed_plan of a model without any effective dropout, or an SG_ERR_* code
+// (embed-once training, include/siamese_embed_train.h)
+int train_plan(const sg_model_t *model, SgGenPlan *P, bool grid) {
+  if (!model) return SG_ERR_ARG;
+  const int rc = grid ? grid_plan(model, P) : embed_plan(model, P);
+  return rc != SG_OK ? rc : plan_no_dropout(model);
 }
 
 int plan_embed_dim(const SgGenPlan &P) {

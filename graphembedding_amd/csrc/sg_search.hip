@@ -12,70 +12,33 @@ namespace {
 
 using sgk::f4;
 
-constexpr int64_t kSegMin = 1024;       // the library's own segment choice lies in
-constexpr int64_t kSegMax = 65536;      // [kSegMin, kSegMax] columns
-constexpr int kListLds = 32768;         // LDS for the lists of a workgroup's queries
-
 // ---------------------------------------------------------------------------
-// How a call is cut: S segments of seg database columns times nqc chunks of qb queries, one
-// workgroup each, and the workspace [Q tables | candidate keys | candidate values].
+// How a call is cut (search_split, sg_search_split.h) and its workspace
+// [Q tables | candidate keys | candidate values].
 // ---------------------------------------------------------------------------
-struct SearchPlan {
-  int64_t seg, nseg, nqc, qb, blocks;
-  int64_t q_bytes, cand, ws_bytes;   // cand: candidate entries, nseg · m · k
+struct SearchPlan : SearchSplit {
+  int64_t q_bytes, ws_bytes;
   size_t lds;
 };
 
 // Every host check that needs no pointer; the SG_ERR_* order is sg_score_grid's, then
-// sg_topk_rows', then seg_cols.
+// search_split's.
 int search_plan(const sg_model_t *model, int64_t m, int64_t n, int32_t k, int64_t seg_cols,
                 SgGenPlan *P, SearchPlan *S) {
   if (!model || m < 0 || n < 0) return SG_ERR_ARG;
-  const int rc = grid_plan(model, P);
+  int rc = grid_plan(model, P);
   if (rc != SG_OK) return rc;
-  if (k < 1) return SG_ERR_ARG;
-  if (k > kTopkMax) return SG_ERR_UNSUPPORTED;
-  if (k > n) return SG_ERR_ARG;
-  if (seg_cols < 0 || (seg_cols & 63) != 0) return SG_ERR_ARG;
-  if (m > kMaxRows || n > kMaxRows) return SG_ERR_UNSUPPORTED;   // n < 2^31 with it
-  const int64_t target = (int64_t)sg_num_cus() * 8;   // workgroups that fill the device
-  const int64_t max_qc = m > 4 ? (m + 3) / 4 : 1;
-  int64_t seg = seg_cols;
-  if (seg == 0) {
-    // a list costs about k (1 + ln(seg / k)) insertions per segment and k rounds over
-    // its k candidates in the merge: segments of 1024 columns per list entry (at least
-    // 4096) amortise both, shorter ones only where the queries alone cannot fill the device
-    seg = 4096;
-    while (seg < 1024 * (int64_t)k) seg <<= 1;   // k <= 64: at most kSegMax
-    while (seg > kSegMin && ((n + seg - 1) / seg) * max_qc < target) seg >>= 1;
-  }
-  if (seg > n) seg = (n + 63) & ~(int64_t)63;   // one segment (k <= n: n >= 1)
-  S->seg = seg;
-  S->nseg = (n + seg - 1) / seg;
-  // query chunks as grid_split cuts them: enough to reach the target, else as many
-  // queries as possible per load of the database tiles, within the LDS of the lists
-  int64_t nqc = (target + S->nseg - 1) / S->nseg;
-  nqc = nqc > max_qc ? max_qc : nqc;
-  int64_t qb = (((m + nqc - 1) / nqc) + 3) & ~(int64_t)3;
-  const int64_t qb_cap = (kListLds / (kListBytes * k)) & ~3;   // >= 40
-  qb = qb > qb_cap ? qb_cap : qb;
-  qb = qb < 4 ? 4 : qb;
-  S->qb = qb;
-  S->nqc = m > 0 ? (m + qb - 1) / qb : 1;
-  S->blocks = S->nseg * S->nqc;
-  if (S->blocks > 0x7FFFFFFF) return SG_ERR_UNSUPPORTED;
-  S->lds = (size_t)qb * k * kListBytes;
+  // 8 workgroups per CU fill the device; 32768 B of LDS for the lists of a workgroup's queries
+  rc = search_split(SearchUnit{(int64_t)sg_num_cus() * 8, 4, 32768}, m, n, k, seg_cols, S);
+  if (rc != SG_OK) return rc;
+  S->lds = (size_t)S->qb * k * kListBytes;
   S->q_bytes = (m * grid_dp(*P) * 16 * 4 + 255) & ~(int64_t)255;
-  S->cand = S->nseg * m * k;
-  // the library's own choice depends on m and on the device: its workspace is sized for
-  // the shortest segments it may pick, so the size is monotone and the same everywhere
-  const int64_t ws_seg = seg_cols == 0 ? (n + kSegMin - 1) / kSegMin : S->nseg;
-  S->ws_bytes = S->q_bytes + ws_seg * m * k * kListBytes + 256;
+  S->ws_bytes = S->q_bytes + S->cand_bytes;
   return SG_OK;
 }
 
-// The running top-k list of a query (list_insert) and the merge of the segments' candidate
-// lists (sg_search_merge_kernel) are shared with sg_web_search.hip: sg_search_lists.h.
+// The running top-k list of a query, its write-out and the merge of the segments' candidate
+// lists are shared with sg_web_search.hip and sg_dot_grid.hip: sg_search_lists.h.
 
 // ---------------------------------------------------------------------------
 // A workgroup owns one segment of the database and one chunk of qb queries.  As in
@@ -90,10 +53,7 @@ int search_plan(const sg_model_t *model, int64_t m, int64_t n, int32_t k, int64_
 struct SearchArgs : GridCommon {   // ncb counts segments here
   int64_t seg;
   int apply_final, k, largest;
-  uint64_t *ckey;   // candidates [nseg][m][k], or
-  float *cval;
-  int32_t *idx;     // with one segment the results themselves [m][k]
-  float *val;       // (may be null)
+  ListOut out;
 };
 
 template <int NS>
@@ -108,8 +68,7 @@ __global__ void __launch_bounds__(256) sg_search_kernel(SearchArgs A) {
   const int64_t c1 = c0 + A.seg < A.n ? c0 + A.seg : A.n;
   uint64_t *lkeys = (uint64_t *)smem;                 // [qb][k]
   float *lvals = (float *)(lkeys + (size_t)A.qb * k);   // [qb][k]
-  for (int64_t i = q0 + wave; i < q1; i += 4)
-    if (lane < k) lkeys[(i - q0) * k + lane] = ~0ull;
+  for (int64_t i = q0 + wave; i < q1; i += 4) list_reset(lkeys + (i - q0) * k, k, lane);
   sg_wsync();
   const float usum = grid_usum(A);
   const GridCol col = grid_col(A, c, usum);   // column k = c of C
@@ -147,11 +106,7 @@ __global__ void __launch_bounds__(256) sg_search_kernel(SearchArgs A) {
       s *= usum;
       if (A.apply_final) s = sg_final(A.final_act, A.yeta, s);
       const uint64_t key = jst < A.n ? topk_key(s, (uint32_t)jst, A.largest) : ~0ull;
-      const uint64_t hits = __ballot(key < thr);
-      if (hits) {
-        list_insert(lk, lvals + (i - q0) * k, k, lane, key, s, hits, thr);
-        sg_wsync();
-      }
+      list_offer(lk, lvals + (i - q0) * k, k, lane, key, s, thr);
     }
   }
   for (int64_t i = q0 + wave; i < q1; i += 4) {
@@ -159,12 +114,12 @@ __global__ void __launch_bounds__(256) sg_search_kernel(SearchArgs A) {
     const uint64_t key = lkeys[(i - q0) * k + lane];
     const float val = lvals[(i - q0) * k + lane];
     if (A.ncb == 1) {   // k <= n: every entry is a column
-      A.idx[i * k + lane] = (int32_t)(uint32_t)key;
-      if (A.val) A.val[i * k + lane] = val;
+      A.out.idx[i * k + lane] = (int32_t)(uint32_t)key;
+      if (A.out.val) A.out.val[i * k + lane] = val;
     } else {   // a short last segment leaves sentinels; their values are never read
       const int64_t o = (sgm * A.m + i) * k + lane;
-      A.ckey[o] = key;
-      A.cval[o] = val;
+      A.out.ckey[o] = key;
+      A.out.cval[o] = val;
     }
   }
 }
@@ -205,17 +160,12 @@ int32_t sg_search_topk(const sg_model_t *model, const float *emb_q, const float 
   A.apply_final = apply_final ? 1 : 0;
   A.k = k;
   A.largest = largest ? 1 : 0;
-  A.ckey = (uint64_t *)((char *)workspace + S.q_bytes);
-  A.cval = (float *)(A.ckey + S.cand);
-  A.idx = idx_out;
-  A.val = val_out;
+  A.out = list_out((char *)workspace + S.q_bytes, S, idx_out, val_out);
   grid_dispatch_ns(grid_dp(P) / 4, [&](auto ns) {
     hipLaunchKernelGGL(sg_search_kernel<decltype(ns)::value>, dim3((unsigned)S.blocks),
                        dim3(256), S.lds, st, A);
   });
-  if (S.nseg > 1)
-    hipLaunchKernelGGL(sg_search_merge_kernel, dim3((unsigned)m), dim3(64), 0, st, A.ckey,
-                       A.cval, m, (int)S.nseg, (int)k, idx_out, val_out);
+  launch_search_merge(A.out, S, m, k, st);
   return hipGetLastError() == hipSuccess ? SG_OK : SG_ERR_HIP;
 }
 

@@ -1,15 +1,17 @@
 // sg_search_lists.h — what the fused search kernels share (sg_search.hip: search at
 // D <= 31, include/siamese_search.h; sg_web_search.hip: search for graph-store models at D in
-// [32, 512], include/siamese_web_search.h): the running top-k list of one query and the
-// kernel that merges the candidate lists of a query's segments.  The key of the total order
-// is topk_key (sg_embed_plan.h).  Internal linkage: each unit compiles its own copy.
+// [32, 512], include/siamese_web_search.h; sg_dot_grid.hip: search for the Dot head,
+// include/siamese_dot_embed.h): the running top-k list of one query, where a kernel leaves
+// its lists, and the kernel that merges the candidate lists of a query's segments.  How a
+// call is cut is sg_search_split.h; the key of the total order is topk_key
+// (sg_embed_plan.h).  Internal linkage: each unit compiles its own copy.
 #pragma once
 #include "sg_embed_plan.h"
+#include "sg_search_split.h"
 
 namespace {
 
-constexpr int kTopkMax = 64;            // one list entry per lane
-constexpr int kListBytes = 12;          // a list entry: 64-bit key + the value's bits
+static_assert(kSearchMaxRows == kMaxRows, "the search's row limit is the grid's");
 
 // ---------------------------------------------------------------------------
 // The running top-k of one query: k keys in ascending order (best first) with the value
@@ -58,6 +60,29 @@ __device__ __forceinline__ void list_insert(uint64_t *lk, float *lv, int k, int 
   }
 }
 
+// An empty list: every key the all-ones sentinel
+__device__ __forceinline__ void list_reset(uint64_t *lk, int k, int lane) {
+  if (lane < k) lk[lane] = ~0ull;
+}
+
+// Lane l offers (key, s) to the list whose threshold thr = lk[k - 1] the caller has read
+__device__ __forceinline__ void list_offer(uint64_t *lk, float *lv, int k, int lane,
+                                           uint64_t key, float s, uint64_t thr) {
+  const uint64_t hits = __ballot(key < thr);
+  if (hits) {
+    list_insert(lk, lv, k, lane, key, s, hits, thr);
+    sg_wsync();
+  }
+}
+
+// Where a search kernel leaves its lists; every *SearchArgs struct embeds one
+struct ListOut {
+  uint64_t *ckey;   // candidates [nseg][m][k], or
+  float *cval;
+  int32_t *idx;     // with one segment the results themselves [m][k]
+  float *val;       // (may be null)
+};
+
 // ---------------------------------------------------------------------------
 // Merge: one wavefront per query picks the k smallest of its nseg · k candidate keys by
 // sg_topk_kernel's selection rounds (keys of distinct columns differ, so "the smallest key
@@ -97,6 +122,24 @@ __global__ void __launch_bounds__(64) sg_search_merge_kernel(const uint64_t *__r
       if (val) val[i * k + r] = cval[bpos];
     }
   }
+}
+
+// The candidate part of a workspace is [keys | values]
+ListOut list_out(void *cand_ws, const SearchSplit &S, int32_t *idx_out, float *val_out) {
+  ListOut O;
+  O.ckey = (uint64_t *)cand_ws;
+  O.cval = (float *)(O.ckey + S.cand);
+  O.idx = idx_out;
+  O.val = val_out;
+  return O;
+}
+
+// The tail of every search call: with more than one segment the candidates are merged
+void launch_search_merge(const ListOut &O, const SearchSplit &S, int64_t m, int32_t k,
+                         hipStream_t st) {
+  if (S.nseg > 1)
+    hipLaunchKernelGGL(sg_search_merge_kernel, dim3((unsigned)m), dim3(64), 0, st, O.ckey,
+                       O.cval, m, (int)S.nseg, (int)k, O.idx, O.val);
 }
 
 }  // namespace

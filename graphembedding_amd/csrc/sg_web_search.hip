@@ -11,8 +11,6 @@
 
 namespace {
 
-constexpr int64_t kWebSegMin = 1024;   // the library's own segment choice lies in
-constexpr int64_t kWebSegMax = 65536;  // [kWebSegMin, kWebSegMax] columns
 // LDS for the lists of a workgroup's queries.  At D = 512 the two table buffers take
 // 66048 B and the hand-over slots 1536 B; with 12288 B of lists a workgroup asks for
 // 79872 B, so two workgroups share a CU's 160 KB at every k (k = 64: 16 queries).
@@ -20,64 +18,29 @@ constexpr int kWebListLds = 12288;
 constexpr int kWebSlotBytes = 2 * 64 * kListBytes;   // two hand-over slots of 64 entries
 
 // ---------------------------------------------------------------------------
-// How a call is cut: S segments of seg database columns times nqc chunks of qb queries, one
-// workgroup each, and the workspace [Q tables | candidate keys | candidate values].
+// How a call is cut (search_split, sg_search_split.h) and its workspace
+// [Q tables | candidate keys | candidate values].
 // ---------------------------------------------------------------------------
-struct WebSearchPlan {
-  int64_t seg, nseg, nqc, qb, blocks;
-  int64_t q_bytes, cand, ws_bytes;   // cand: candidate entries, nseg · m · k
+struct WebSearchPlan : SearchSplit {
+  int64_t q_bytes, ws_bytes;
   size_t lds;
 };
 
 // Every host check that needs no pointer: sg_web_score_grid's for the model, then
-// sg_search_topk's for k, seg_cols, m and n.
+// search_split's for k, seg_cols, m and n.
 int web_search_plan(const sg_model_t *model, int64_t m, int64_t n, int32_t k, int64_t seg_cols,
                     SgWebHead *H, WebSearchPlan *S) {
   if (!model || m < 0 || n < 0) return SG_ERR_ARG;
-  const int rc = sg_web_head_plan(model, H);
+  int rc = sg_web_head_plan(model, H);
   if (rc != SG_OK) return rc;
   if (H->K > kGridMaxK) return SG_ERR_UNSUPPORTED;
-  if (k < 1) return SG_ERR_ARG;
-  if (k > kTopkMax) return SG_ERR_UNSUPPORTED;
-  if (k > n) return SG_ERR_ARG;
-  if (seg_cols < 0 || (seg_cols & 63) != 0) return SG_ERR_ARG;
-  if (m > kMaxRows || n > kMaxRows) return SG_ERR_UNSUPPORTED;   // n < 2^31 with it
   // two workgroups per CU hold the device, as for the grid (2 x 78 KB of LDS at D = 512)
-  const int64_t target = (int64_t)sg_num_cus() * 2;
-  const int64_t max_qc = m > 4 ? (m + 3) / 4 : 1;
-  int64_t seg = seg_cols;
-  if (seg == 0) {
-    // as search_plan (sg_search.hip): a list costs about k (1 + ln(seg / k)) insertions
-    // per segment and k rounds over its k candidates in the merge: segments of 1024 columns
-    // per list entry (at least 4096) amortise both, shorter ones only where the queries
-    // alone cannot fill the device
-    seg = 4096;
-    while (seg < 1024 * (int64_t)k) seg <<= 1;   // k <= 64: at most kWebSegMax
-    while (seg > kWebSegMin && ((n + seg - 1) / seg) * max_qc < target) seg >>= 1;
-  }
-  if (seg > n) seg = (n + 63) & ~(int64_t)63;   // one segment (k <= n: n >= 1)
-  S->seg = seg;
-  S->nseg = (n + seg - 1) / seg;
-  // query chunks as grid_split cuts them: enough to reach the target, else as many queries
-  // as possible per load of the database tiles, within the LDS of the lists
-  int64_t nqc = (target + S->nseg - 1) / S->nseg;
-  nqc = nqc > max_qc ? max_qc : nqc;
-  int64_t qb = (((m + nqc - 1) / nqc) + 3) & ~(int64_t)3;
-  const int64_t qb_cap = (kWebListLds / (kListBytes * k)) & ~3;   // >= 16
-  qb = qb > qb_cap ? qb_cap : qb;
-  qb = qb < 4 ? 4 : qb;
-  S->qb = qb;
-  S->nqc = m > 0 ? (m + qb - 1) / qb : 1;
-  S->blocks = S->nseg * S->nqc;
-  if (S->blocks > 0x7FFFFFFF) return SG_ERR_UNSUPPORTED;
+  rc = search_split(SearchUnit{(int64_t)sg_num_cus() * 2, 4, kWebListLds}, m, n, k, seg_cols, S);
+  if (rc != SG_OK) return rc;
   const int ns = web_dq(H->D) / 4;
-  S->lds = (size_t)2 * ns * 256u + (size_t)qb * k * kListBytes + kWebSlotBytes;
+  S->lds = (size_t)2 * ns * 256u + (size_t)S->qb * k * kListBytes + kWebSlotBytes;
   S->q_bytes = (m * web_dq(H->D) * 16 * 4 + 255) & ~(int64_t)255;
-  S->cand = S->nseg * m * k;
-  // the library's own choice depends on m and on the device: its workspace is sized for
-  // the shortest segments it may pick, so the size is monotone and the same everywhere
-  const int64_t ws_seg = seg_cols == 0 ? (n + kWebSegMin - 1) / kWebSegMin : S->nseg;
-  S->ws_bytes = S->q_bytes + ws_seg * m * k * kListBytes + 256;
+  S->ws_bytes = S->q_bytes + S->cand_bytes;
   return SG_OK;
 }
 
@@ -106,10 +69,7 @@ struct WebSearchArgs : GridCommon {   // ncb counts segments here
   int64_t ld_db, seg;
   int ns;
   int apply_final, k, largest;
-  uint64_t *ckey;   // candidates [nseg][m][k], or
-  float *cval;
-  int32_t *idx;     // with one segment the results themselves [m][k]
-  float *val;       // (may be null)
+  ListOut out;
 };
 
 // the slot of parity p into the list of local query qi, by the wavefront that owns it
@@ -119,12 +79,7 @@ __device__ __forceinline__ void web_search_take(const uint64_t *skey, const floa
   const uint64_t key = skey[p * 64 + lane];
   const float s = sval[p * 64 + lane];
   uint64_t *lk = lkeys + qi * k;
-  const uint64_t thr = lk[k - 1];
-  const uint64_t hits = __ballot(key < thr);
-  if (hits) {
-    list_insert(lk, lvals + qi * k, k, lane, key, s, hits, thr);
-    sg_wsync();
-  }
+  list_offer(lk, lvals + qi * k, k, lane, key, s, lk[k - 1]);
 }
 
 template <int NSMAX>
@@ -146,8 +101,7 @@ __global__ void __launch_bounds__(256) web_search_kernel(WebSearchArgs A) {
   uint64_t *skey = lkeys + (size_t)A.qb * k;
   float *lvals = (float *)(skey + 2 * 64);
   float *sval = lvals + (size_t)A.qb * k;
-  for (int64_t qi = wave; qi < q1 - q0; qi += 4)
-    if (lane < k) lkeys[qi * k + lane] = ~0ull;
+  for (int64_t qi = wave; qi < q1 - q0; qi += 4) list_reset(lkeys + qi * k, k, lane);
   const float usum = grid_usum(A);
   const GridCol col = grid_col(A, c, usum);   // column k = c of C
   const bool kmask = col.mask;
@@ -192,12 +146,12 @@ __global__ void __launch_bounds__(256) web_search_kernel(WebSearchArgs A) {
     const uint64_t key = lkeys[qi * k + lane];
     const float val = lvals[qi * k + lane];
     if (A.ncb == 1) {   // k <= n: every entry is a column
-      A.idx[i * k + lane] = (int32_t)(uint32_t)key;
-      if (A.val) A.val[i * k + lane] = val;
+      A.out.idx[i * k + lane] = (int32_t)(uint32_t)key;
+      if (A.out.val) A.out.val[i * k + lane] = val;
     } else {   // a short last segment leaves sentinels; their values are never read
       const int64_t o = (sgm * A.m + i) * k + lane;
-      A.ckey[o] = key;
-      A.cval[o] = val;
+      A.out.ckey[o] = key;
+      A.out.cval[o] = val;
     }
   }
 }
@@ -246,16 +200,11 @@ int32_t sg_web_search_topk(const sg_model_t *model, const float *emb_q, int64_t 
   A.apply_final = apply_final ? 1 : 0;
   A.k = k;
   A.largest = largest ? 1 : 0;
-  A.ckey = (uint64_t *)((char *)Q + S.q_bytes);   // 16-byte aligned, as Q is
-  A.cval = (float *)(A.ckey + S.cand);
-  A.idx = idx_out;
-  A.val = val_out;
+  A.out = list_out((char *)Q + S.q_bytes, S, idx_out, val_out);   // 16-byte aligned, as Q is
   web_dispatch_nsmax(A.ns, [&](auto nsmax) {
     web_search_launch<decltype(nsmax)::value>(A, S, st);
   });
-  if (S.nseg > 1)
-    hipLaunchKernelGGL(sg_search_merge_kernel, dim3((unsigned)m), dim3(64), 0, st, A.ckey,
-                       A.cval, m, (int)S.nseg, (int)k, idx_out, val_out);
+  launch_search_merge(A.out, S, m, k, st);
   return hipGetLastError() == hipSuccess ? SG_OK : SG_ERR_HIP;
 }
 

@@ -145,6 +145,48 @@ class GridProblem:
         _lib.check(int(self.status.item()), 'embed-once training (device status)')
 
 
+class _Family(object):
+    """How a model's family talks to the library in the embed-once calls: the ctypes wrappers
+    it uses (a name that is None: the family has no such call) and what differs in their
+    argument lists.
+      strided  the grid calls take embeddings with a row stride, else contiguous [*, E] copies
+      params   the grid calls take the parameter vector (the Dot head has no variables)
+      web      the store is a CsrStore's struct, the embedding buffers are [*][ld] rows, the
+               embed calls take a workspace and the backward calls the gradients' row stride"""
+
+    def __init__(self, strided, params, web, **calls):
+        self.strided, self.params, self.web = strided, params, web
+        self.__dict__.update(calls)
+
+
+_NODE_STACK = dict(embed=_lib.embed, embed_drop=_lib.embed_drop, embed_bwd=_lib.embed_bwd,
+                   embed_drop_bwd=_lib.embed_drop_bwd, embed_ws=None, embed_drop_ws=None,
+                   embed_bwd_ws=_lib.embed_bwd_workspace_bytes,
+                   embed_drop_bwd_ws=_lib.embed_drop_bwd_workspace_bytes)
+_FAMILIES = {
+    'ntn': _Family(strided=False, params=True, web=False, grid=_lib.score_grid,
+                   grid_ws=_lib.score_grid_workspace_bytes, search=_lib.search_topk,
+                   search_ws=_lib.search_workspace_bytes,
+                   grid_fwd_bwd=_lib.score_grid_fwd_bwd,
+                   grid_bwd_ws=_lib.score_grid_bwd_workspace_bytes, **_NODE_STACK),
+    'dot': _Family(strided=True, params=False, web=False, grid=_lib.dot_score_grid, grid_ws=None,
+                   search=_lib.dot_search_topk, search_ws=_lib.dot_search_workspace_bytes,
+                   grid_fwd_bwd=_lib.dot_score_grid_fwd_bwd,
+                   grid_bwd_ws=_lib.dot_score_grid_bwd_workspace_bytes, **_NODE_STACK),
+    'web': _Family(strided=True, params=True, web=True, grid=_lib.web_score_grid,
+                   grid_ws=_lib.web_score_grid_workspace_bytes, search=_lib.web_search_topk,
+                   search_ws=_lib.web_search_workspace_bytes,
+                   grid_fwd_bwd=_lib.web_score_grid_fwd_bwd,
+                   grid_bwd_ws=_lib.web_score_grid_bwd_workspace_bytes,
+                   embed=_lib.web_embed, embed_drop=_lib.web_embed_drop,
+                   embed_bwd=_lib.web_embed_bwd, embed_drop_bwd=_lib.web_embed_drop_bwd,
+                   embed_ws=_lib.web_embed_workspace_bytes,
+                   embed_drop_ws=_lib.web_embed_drop_workspace_bytes,
+                   embed_bwd_ws=_lib.web_embed_bwd_workspace_bytes,
+                   embed_drop_bwd_ws=_lib.web_embed_drop_bwd_workspace_bytes),
+}
+
+
 class SiameseGCNTNMSE(object):
     def __init__(self, input_dim, flags=None, device='cuda', n_max=None, params=None):
         f = flags or FLAGS
@@ -180,6 +222,8 @@ class SiameseGCNTNMSE(object):
                 if path2:
                     self.sg, self.n_max, self.n_params, self.kernel_path = sg2, cap, n2, path2
                     break
+        # the family of the embed-once calls (_Family)
+        self._family = _FAMILIES['web' if self.is_web else 'dot' if self.is_dot else 'ntn']
         import torch
         self.torch = torch
         init = glorot_flat(self.layers, self.input_dim, f.param_seed) if params is None else \
@@ -528,12 +572,23 @@ class SiameseGCNTNMSE(object):
     def test_scores(self, batch: Batch, seed=None):
         return self.pred_sim_without_act(batch, seed).cpu().numpy().astype(np.float64)
 
-    # ---- embed-once retrieval (include/siamese_embed.h; inference mode: no dropout) ----
+    # ---- embed-once retrieval, search and training ------------------------------------------
+    # A model belongs to one family (_Family above): 'ntn' (include/siamese_embed.h,
+    # siamese_search.h, siamese_embed_train.h, siamese_embed_drop.h), 'dot' (the node-stack
+    # calls of 'ntn', the grid calls of include/siamese_dot_embed.h) or 'web', graph-store
+    # models (include/siamese_web_*.h).  _embed, _score_grid, _search, _grid_problem,
+    # _grid_fwd_bwd and _grid_train_step are each written once on the family; the public
+    # methods below them apply their refusal and name themselves in the messages.
     def _no_web(self, what):
         if self.is_web:
             raise _lib.SiameseHipError('{}: graph-store (Web) models have no embedding '
                                        'kernels here; use web_embed / web_score_grid / '
                                        'web_search / topk'.format(what))
+
+    def _only_web(self, what):
+        if not self.is_web:
+            raise _lib.SiameseHipError('{}: the model is not on the graph-store (Web) path; '
+                                       'use embed / score_grid'.format(what))
 
     @property
     def is_dot(self) -> bool:
@@ -541,12 +596,36 @@ class SiameseGCNTNMSE(object):
         include/siamese_dot_embed.h serve it, the NTN grid calls every other model."""
         return self.layers[-1]['kind'] == 'Dot'
 
-    def _dot_rows(self, e, what):
-        """(tensor, row stride) of embeddings [*, E] as the Dot grid calls take them: a tensor
-        with unit inner stride and a row stride >= E is passed on as it is, anything else is
-        copied."""
+    @property
+    def embed_dim(self) -> int:
+        """Width of one graph embedding: the pair head's per-graph input."""
+        self._no_web('embed_dim')
+        return _lib.embed_dim(self.sg)
+
+    @property
+    def web_embed_dim(self) -> int:
+        """Width D of one graph embedding of a graph-store model: the Padding / NTN width."""
+        self._only_web('web_embed_dim')
+        return _lib.web_embed_dim(self.sg)
+
+    def _embed_dims(self):
+        """(width, row stride) of the embedding buffers: [*][E], or for graph-store models the
+        [*][ld] rows of sg_web_embed (ld = D rounded up to 128)."""
+        if self._family.web:
+            return _lib.web_embed_dim(self.sg), _lib.web_embed_ld(self.sg)
+        return 2 * (_lib.embed_dim(self.sg),)
+
+    def _f32(self, shape, new=None):
+        return (new or self.torch.empty)(shape, dtype=self.torch.float32, device=self.device)
+
+    def _new_ws(self, nbytes):
+        return self._f32(nbytes // 4 + 1)
+
+    def _rows(self, e, d, what):
+        """(tensor, row stride) of embeddings [*, d] as the strided grid calls take them: a
+        tensor with unit inner stride and a row stride >= d is passed on as it is (the
+        web_embed view with its stride of 128 or more), anything else is copied."""
         torch = self.torch
-        d = self.embed_dim
         e = torch.as_tensor(e, dtype=torch.float32, device=self.device)
         if e.dim() != 2 or e.shape[1] != d:
             raise _lib.SiameseHipError('{}: embeddings must be [*, {}]'.format(what, d))
@@ -554,56 +633,82 @@ class SiameseGCNTNMSE(object):
             e = e.contiguous()
         return e, (int(e.stride(0)) if e.shape[0] > 1 else max(d, int(e.stride(0))))
 
-    @property
-    def embed_dim(self) -> int:
-        """Width of one graph embedding: the pair head's per-graph input."""
-        self._no_web('embed_dim')
-        return _lib.embed_dim(self.sg)
+    def _grid_operands(self, emb_q, emb_db, what):
+        """(what every grid call starts with, m, n): the embeddings, with their row strides or
+        as contiguous [*, E] copies, the two counts, and the parameters if the head has any."""
+        fam, d = self._family, self._embed_dims()[0]
+        (q, ld_q), (db, ld_db) = (self._rows(e, d, what) for e in (emb_q, emb_db))
+        m, n = int(q.shape[0]), int(db.shape[0])
+        ops = [q, ld_q, db, ld_db] if fam.strided else [q.contiguous(), db.contiguous()]
+        return ops + [m, n] + ([self.params] if fam.params else []), m, n
 
-    def embed(self, store: GraphStore, graph_idx=None):
-        """Graph-level embeddings [count][embed_dim] (torch, on the device) of the graphs
-        graph_idx (store ids, repeats allowed; None = every graph) of a GraphStore built at
-        this model's n_max.  Dropout is off whatever flags.dropout says."""
-        torch = self.torch
-        self._no_web('embed')
-        self._check_store_capacity(store)
-        self.check_node_counts(store.n, 'embed')
+    def _node_args(self, store_dev, idx, count, seed):
+        """What every node-stack call starts with; seed: None, or the step's seed of graph-keyed
+        dropout (entry c is side c & 1 of unit c >> 1: entry_offset 0)."""
+        store = [store_dev] if self._family.web else [store_dev, self.n_max]
+        return store + [idx, count] + ([self.params] if seed is None else [0, self.params, seed])
+
+    def _embed_call(self, store_dev, idx, count, seed, out, ws, status):
+        """sg_embed, or with a seed sg_embed_drop (sg_web_*: with their workspace), under the
+        model's own struct."""
+        fam = self._family
+        (fam.embed if seed is None else fam.embed_drop)(
+            self.sg, *self._node_args(store_dev, idx, count, seed), out,
+            *([ws] if fam.web else []), status)
+
+    def _embed(self, what, store, graph_idx):
+        torch, fam = self.torch, self._family
+        if not fam.web:
+            self._check_store_capacity(store)
+        self.check_node_counts(store.n, what)
         idx = None
         count = len(store)
         if graph_idx is not None:
             idx = torch.as_tensor(graph_idx, dtype=torch.int32, device=self.device).reshape(-1)
             idx = idx.contiguous()
             count = int(idx.numel())
-        out = torch.empty((count, self.embed_dim), dtype=torch.float32, device=self.device)
+        d, ld = self._embed_dims()
+        out = self._f32((count, ld))
         status = torch.zeros(1, dtype=torch.int32, device=self.device)
-        _lib.embed(self.sg, store.to_device(self.device), store.n_max, idx, count, self.params,
-                   out, status)
-        _lib.check(int(status.item()), 'sg_embed (device status)')
+        ws = self._new_ws(fam.embed_ws(self.sg, count)) if fam.web else None
+        self._embed_call(store.to_device(self.device), idx, count, None, out, ws, status)
+        _lib.check(int(status.item()), 'sg_{} (device status)'.format(what))
+        return out if ld == d else out[:, :d]
+
+    def _score_grid(self, what, emb_q, emb_db, final):
+        fam = self._family
+        ops, m, n = self._grid_operands(emb_q, emb_db, what)
+        ws = [self._new_ws(fam.grid_ws(self.sg, m))] if fam.grid_ws else []   # Dot: no workspace
+        out = self._f32((m, n))
+        fam.grid(self.sg, *ops, final, out, n, *ws)
         return out
+
+    def _search(self, what, emb_q, emb_db, k, largest, final, seg_cols):
+        torch, fam = self.torch, self._family
+        ops, m, n = self._grid_operands(emb_q, emb_db, what)
+        nbytes = fam.search_ws(self.sg, m, n, k, seg_cols)
+        ws = getattr(self, '_search_ws', None)      # the last workspace, kept while it fits
+        if ws is None or ws.numel() * 4 < nbytes or ws.device != ops[0].device:
+            ws = self._new_ws(nbytes)
+            self._search_ws = ws
+        idx = torch.empty((m, int(k)), dtype=torch.int32, device=self.device)
+        val = self._f32((m, int(k)))
+        fam.search(self.sg, *ops, final, k, largest, seg_cols, idx, val, ws)
+        return idx, val
+
+    def embed(self, store: GraphStore, graph_idx=None):
+        """Graph-level embeddings [count][embed_dim] (torch, on the device) of the graphs
+        graph_idx (store ids, repeats allowed; None = every graph) of a GraphStore built at
+        this model's n_max.  Dropout is off whatever flags.dropout says."""
+        self._no_web('embed')
+        return self._embed('embed', store, graph_idx)
 
     def score_grid(self, emb_q, emb_db, final=True):
         """Scores [m][n] of (query i as graph 1, database j as graph 2) from embeddings
         (embed): the similarity (final activation applied) or, final=False, the
         pre-activation score of pred_sim_without_act."""
-        torch = self.torch
         self._no_web('score_grid')
-        if self.is_dot:
-            (q, ld_q), (db, ld_db) = (self._dot_rows(e, 'score_grid') for e in (emb_q, emb_db))
-            m, n = int(q.shape[0]), int(db.shape[0])
-            out = torch.empty((m, n), dtype=torch.float32, device=self.device)
-            _lib.dot_score_grid(self.sg, q, ld_q, db, ld_db, m, n, final, out, n)
-            return out
-        d = self.embed_dim
-        q = torch.as_tensor(emb_q, dtype=torch.float32, device=self.device).contiguous()
-        db = torch.as_tensor(emb_db, dtype=torch.float32, device=self.device).contiguous()
-        if q.dim() != 2 or db.dim() != 2 or q.shape[1] != d or db.shape[1] != d:
-            raise _lib.SiameseHipError('score_grid: embeddings must be [*, {}]'.format(d))
-        m, n = int(q.shape[0]), int(db.shape[0])
-        ws = torch.empty(_lib.score_grid_workspace_bytes(self.sg, m) // 4 + 1,
-                         dtype=torch.float32, device=self.device)
-        out = torch.empty((m, n), dtype=torch.float32, device=self.device)
-        _lib.score_grid(self.sg, q, db, m, n, self.params, final, out, n, ws)
-        return out
+        return self._score_grid('score_grid', emb_q, emb_db, final)
 
     def topk(self, scores, k, largest=True):
         """(idx int32 [m][k], values [m][k]) of the k best entries of each row of scores:
@@ -624,103 +729,25 @@ class SiameseGCNTNMSE(object):
         largest), bit for bit, from one fused call that never holds the [m][n] scores
         (include/siamese_search.h).  seg_cols: database columns per workgroup, 0 = the
         library's choice; the result does not depend on it."""
-        torch = self.torch
         self._no_web('search')
-        if self.is_dot:
-            (q, ld_q), (db, ld_db) = (self._dot_rows(e, 'search') for e in (emb_q, emb_db))
-            m, n = int(q.shape[0]), int(db.shape[0])
-            nbytes = _lib.dot_search_workspace_bytes(self.sg, m, n, k, seg_cols)
-            ws = getattr(self, '_search_ws', None)      # the last workspace, kept while it fits
-            if ws is None or ws.numel() * 4 < nbytes or ws.device != q.device:
-                ws = torch.empty(nbytes // 4 + 1, dtype=torch.float32, device=self.device)
-                self._search_ws = ws
-            idx = torch.empty((m, int(k)), dtype=torch.int32, device=self.device)
-            val = torch.empty((m, int(k)), dtype=torch.float32, device=self.device)
-            _lib.dot_search_topk(self.sg, q, ld_q, db, ld_db, m, n, final, k, largest, seg_cols,
-                                 idx, val, ws)
-            return idx, val
-        d = self.embed_dim
-        q = torch.as_tensor(emb_q, dtype=torch.float32, device=self.device).contiguous()
-        db = torch.as_tensor(emb_db, dtype=torch.float32, device=self.device).contiguous()
-        if q.dim() != 2 or db.dim() != 2 or q.shape[1] != d or db.shape[1] != d:
-            raise _lib.SiameseHipError('search: embeddings must be [*, {}]'.format(d))
-        m, n = int(q.shape[0]), int(db.shape[0])
-        nbytes = _lib.search_workspace_bytes(self.sg, m, n, k, seg_cols)
-        ws = getattr(self, '_search_ws', None)      # the last workspace, kept while it fits
-        if ws is None or ws.numel() * 4 < nbytes or ws.device != q.device:
-            ws = torch.empty(nbytes // 4 + 1, dtype=torch.float32, device=self.device)
-            self._search_ws = ws
-        idx = torch.empty((m, int(k)), dtype=torch.int32, device=self.device)
-        val = torch.empty((m, int(k)), dtype=torch.float32, device=self.device)
-        _lib.search_topk(self.sg, q, db, m, n, self.params, final, k, largest, seg_cols, idx,
-                         val, ws)
-        return idx, val
+        return self._search('search', emb_q, emb_db, k, largest, final, seg_cols)
 
     # ---- embed-once retrieval for graph-store models (include/siamese_web_embed.h) ----
-    def _only_web(self, what):
-        if not self.is_web:
-            raise _lib.SiameseHipError('{}: the model is not on the graph-store (Web) path; '
-                                       'use embed / score_grid'.format(what))
-
-    @property
-    def web_embed_dim(self) -> int:
-        """Width D of one graph embedding of a graph-store model: the Padding / NTN width."""
-        self._only_web('web_embed_dim')
-        return _lib.web_embed_dim(self.sg)
-
     def web_embed(self, store, graph_idx=None):
         """Graph-level embeddings [count][D] (torch, on the device) of the graphs graph_idx
         (store ids, repeats allowed; None = every graph) of a web.CsrStore.  The tensor is a
         view of the [count][ld] buffer the kernel writes (ld = D rounded up to 128): it keeps
         that row stride.  Dropout is off whatever flags.dropout says."""
-        torch = self.torch
         self._only_web('web_embed')
-        self.check_node_counts(store.n, 'web_embed')
-        idx = None
-        count = len(store)
-        if graph_idx is not None:
-            idx = torch.as_tensor(graph_idx, dtype=torch.int32, device=self.device).reshape(-1)
-            idx = idx.contiguous()
-            count = int(idx.numel())
-        d, ld = _lib.web_embed_dim(self.sg), _lib.web_embed_ld(self.sg)
-        out = torch.empty((count, ld), dtype=torch.float32, device=self.device)
-        status = torch.zeros(1, dtype=torch.int32, device=self.device)
-        ws = torch.empty(_lib.web_embed_workspace_bytes(self.sg, count) // 4 + 1,
-                         dtype=torch.float32, device=self.device)
-        _lib.web_embed(self.sg, store.to_device(self.device), idx, count, self.params, out, ws,
-                       status)
-        _lib.check(int(status.item()), 'sg_web_embed (device status)')
-        return out[:, :d]
+        return self._embed('web_embed', store, graph_idx)
 
     def web_score_grid(self, emb_q, emb_db, final=True):
         """Scores [m][n] of (query i as graph 1, database j as graph 2) from embeddings
         (web_embed, or any 2-D float32 tensors [*, D] with unit inner stride: their row
         strides are passed on): the similarity, or, final=False, the pre-activation score
         of pred_sim_without_act."""
-        torch = self.torch
         self._only_web('web_score_grid')
-        (q, ld_q), (db, ld_db) = (self._web_rows(e, 'web_score_grid') for e in (emb_q, emb_db))
-        m, n = int(q.shape[0]), int(db.shape[0])
-        ws = torch.empty(_lib.web_score_grid_workspace_bytes(self.sg, m) // 4 + 1,
-                         dtype=torch.float32, device=self.device)
-        out = torch.empty((m, n), dtype=torch.float32, device=self.device)
-        _lib.web_score_grid(self.sg, q, ld_q, db, ld_db, m, n, self.params, final, out, n, ws)
-        return out
-
-    def _web_rows(self, e, what):
-        """(tensor, row stride) of embeddings [*, D] as the web_* grid calls take them: a
-        tensor with unit inner stride and a row stride >= D is passed on as it is (the
-        web_embed view with its stride of 128 or more), anything else is copied."""
-        torch = self.torch
-        d = _lib.web_embed_dim(self.sg)
-        e = torch.as_tensor(e, dtype=torch.float32, device=self.device)
-        if e.dim() != 2 or e.shape[1] != d:
-            raise _lib.SiameseHipError('{}: embeddings must be [*, {}]'.format(what, d))
-        if e.shape[0] > 1 and (e.stride(1) != 1 or e.stride(0) < d):
-            e = e.contiguous()
-        elif e.shape[0] <= 1 and e.stride(1) != 1:
-            e = e.contiguous()
-        return e, (int(e.stride(0)) if e.shape[0] > 1 else max(d, int(e.stride(0))))
+        return self._score_grid('web_score_grid', emb_q, emb_db, final)
 
     def web_search(self, emb_q, emb_db, k, largest=True, final=True, seg_cols=0):
         """(idx int32 [m][k], values [m][k]): topk(web_score_grid(emb_q, emb_db, final), k,
@@ -728,23 +755,12 @@ class SiameseGCNTNMSE(object):
         (include/siamese_web_search.h).  Row strides are handled as web_score_grid handles
         them.  seg_cols: database columns per workgroup, 0 = the library's choice; the result
         does not depend on it."""
-        torch = self.torch
         self._only_web('web_search')
-        (q, ld_q), (db, ld_db) = (self._web_rows(e, 'web_search') for e in (emb_q, emb_db))
-        m, n = int(q.shape[0]), int(db.shape[0])
-        nbytes = _lib.web_search_workspace_bytes(self.sg, m, n, k, seg_cols)
-        ws = getattr(self, '_web_search_ws', None)   # the last workspace, kept while it fits
-        if ws is None or ws.numel() * 4 < nbytes or ws.device != q.device:
-            ws = torch.empty(nbytes // 4 + 1, dtype=torch.float32, device=self.device)
-            self._web_search_ws = ws
-        idx = torch.empty((m, int(k)), dtype=torch.int32, device=self.device)
-        val = torch.empty((m, int(k)), dtype=torch.float32, device=self.device)
-        _lib.web_search_topk(self.sg, q, ld_q, db, ld_db, m, n, self.params, final, k, largest,
-                             seg_cols, idx, val, ws)
-        return idx, val
+        return self._search('web_search', emb_q, emb_db, k, largest, final, seg_cols)
 
-    # ---- embed-once training (include/siamese_embed_train.h: dropout 0 only;
-    # include/siamese_embed_drop.h: dropout='graph', masks keyed per graph) ----
+    # ---- embed-once training (include/siamese_embed_train.h, siamese_web_embed_train.h:
+    # dropout 0 only; include/siamese_embed_drop.h, siamese_web_embed_drop.h: dropout='graph',
+    # masks keyed per graph) ----
     def _no_dropout(self, what):
         if self.flags.dropout != 0:
             raise _lib.SiameseHipError(
@@ -772,6 +788,104 @@ class SiameseGCNTNMSE(object):
             self._sg_keep1_copy = m
         return m
 
+    def _grid_problem(self, what, store, labels, q_idx, db_idx, y_stats, dropout):
+        torch, fam = self.torch, self._family
+        self._grid_dropout(dropout, what)
+        if not fam.web:
+            self._check_store_capacity(store)
+        self.check_node_counts(store.n, what)
+        G = len(store)
+        if G == 0 or int(np.asarray(store.n).min()) < 1:
+            raise _lib.SiameseHipError('{}: every store graph needs at least one '
+                                       'node'.format(what))
+        q = np.arange(G) if q_idx is None else np.asarray(q_idx, np.int64).reshape(-1)
+        db = np.arange(G) if db_idx is None else np.asarray(db_idx, np.int64).reshape(-1)
+        both = np.concatenate([q, db])
+        if both.size and (both.min() < 0 or both.max() >= G):
+            raise _lib.SiameseHipError('{}: graph ids must lie in [0, {})'.format(what, G))
+        uniq, inv = np.unique(both, return_inverse=True)
+        m, n, dev = int(q.size), int(db.size), self.device
+        lab = torch.as_tensor(labels if torch.is_tensor(labels) else
+                              np.asarray(labels, np.float32), dtype=torch.float32,
+                              device=dev).contiguous()
+        if tuple(lab.shape) != (m, n):
+            raise _lib.SiameseHipError('{}: labels must be [{}][{}]'.format(what, m, n))
+        if y_stats is None:
+            y_stats = _label_stats(torch, lab, m * n)
+        ld, U = self._embed_dims()[1], int(uniq.size)
+        # graph-store models: the gradient buffers start as zeros, because the kernels leave
+        # columns [D, ld) untouched, and the Python store is kept alive beside its struct
+        grad = torch.zeros if fam.web else torch.empty
+        store_dev = store.to_device(dev)
+        bwd_ws = fam.embed_drop_bwd_ws if dropout else fam.embed_bwd_ws
+        fwd_ws = fam.embed_drop_ws if dropout else fam.embed_ws
+        return GridProblem(
+            store_dev=(store, store_dev) if fam.web else store_dev, m=m, n=n, labels=lab,
+            y_stats=y_stats, uniq=torch.from_numpy(uniq.astype(np.int32)).to(dev),
+            q_pos=torch.from_numpy(inv[:m].astype(np.int64)).to(dev),
+            db_pos=torch.from_numpy(inv[m:].astype(np.int64)).to(dev),
+            identity=bool(m == n == U and np.array_equal(q, uniq) and np.array_equal(db, uniq)),
+            emb=self._f32((U, ld)), g_emb=self._f32((U, ld), grad),
+            g_q=self._f32((m, ld), grad), g_db=self._f32((n, ld), grad),
+            status=torch.zeros(1, dtype=torch.int32, device=dev),
+            ws_grid=self._new_ws(fam.grid_bwd_ws(self._sg_keep1() if dropout else self.sg, m, n)),
+            ws_embed=self._new_ws(bwd_ws(self.sg, U)),
+            ws_fwd=self._new_ws(fwd_ws(self.sg, U)) if fam.web else None, dropout=dropout)
+
+    def _grid_fwd_bwd(self, what, problem, store, labels, q_idx, db_idx, add_label_term, s_out,
+                      dropout, seed):
+        """The grid step: embed the distinct graphs, run the grid forward and backward, sum the
+        role gradients, run the node-stack backward.  problem: the public *grid_problem."""
+        fam = self._family
+        if isinstance(store, GridProblem):
+            gp = store
+            if dropout is not None and dropout != gp.dropout:
+                raise _lib.SiameseHipError('{}: dropout={!r} on a {} built with '
+                                           'dropout={!r}'.format(what, dropout, problem.__name__,
+                                                                 gp.dropout))
+            self._grid_dropout(gp.dropout, what)
+        else:
+            self._grid_dropout(dropout, what)
+            gp = problem(store, labels, q_idx, db_idx, dropout=dropout)
+        if fam.web and gp.ws_fwd is None:
+            raise _lib.SiameseHipError('{}: the problem was built by grid_problem; use '
+                                       'web_grid_problem'.format(what))
+        store_dev = gp.store_dev[1] if fam.web else gp.store_dev
+        U, ld = int(gp.uniq.numel()), int(gp.emb.shape[1])
+        # dropout='graph': the step's seed, and for the grid the model with keep_prob 1 (the
+        # masks are in the embeddings); the node-stack calls take the model itself
+        seed = self._seed(seed) if gp.dropout else None
+        sg = self._sg_keep1() if gp.dropout else self.sg
+        self._embed_call(store_dev, gp.uniq, U, seed, gp.emb, gp.ws_fwd, gp.status)
+        eq, edb = (gp.emb, gp.emb) if gp.identity else (gp.emb[gp.q_pos], gp.emb[gp.db_pos])
+        # a head without variables (Dot) takes no params and writes no gradient of its own: the
+        # node-stack backward writes all of grad
+        head = [self.params] if fam.params else []
+        fam.grid_fwd_bwd(sg, *([eq, ld, edb, ld] if fam.strided else [eq, edb]), gp.m, gp.n,
+                         *head, gp.labels, gp.n, gp.m * gp.n, gp.y_stats, add_label_term, s_out,
+                         gp.n, *([gp.g_q, ld, gp.g_db, ld] if fam.web else [gp.g_q, gp.g_db]),
+                         *([self.grad] if fam.params else []), self.loss_buf, gp.ws_grid)
+        if gp.identity:
+            self.torch.add(gp.g_q, gp.g_db, out=gp.g_emb)
+        else:
+            gp.g_emb.zero_()
+            gp.g_emb.index_add_(0, gp.q_pos, gp.g_q)
+            gp.g_emb.index_add_(0, gp.db_pos, gp.g_db)
+        (fam.embed_drop_bwd if gp.dropout else fam.embed_bwd)(
+            self.sg, *self._node_args(store_dev, gp.uniq, U, seed), gp.g_emb,
+            *([ld] if fam.web else []), self.grad, gp.ws_embed, gp.status)
+        return gp
+
+    def _grid_train_step(self, fwd_bwd, store, labels, q_idx, db_idx, sync, dropout):
+        fwd_bwd(store, labels, q_idx, db_idx, dropout=dropout)
+        if self.grad_hook is not None:
+            self.grad_hook(self)
+        self.apply_adam()
+        self.step_count += 1
+        if not sync:
+            return None
+        return float(self.loss_buf[0].item() + self.reg_buf[0].item())
+
     def grid_problem(self, store: GraphStore, labels, q_idx=None, db_idx=None, y_stats=None,
                      dropout=None):
         """The device-resident state of an m x n block of pairs (query q_idx[i] as graph 1,
@@ -781,48 +895,8 @@ class SiameseGCNTNMSE(object):
         Build once, step many times (grid_fwd_bwd / grid_train_step).
         dropout: None serves flags.dropout = 0 only; 'graph' trains with dropout masks keyed
         per graph (grid_fwd_bwd) and is stored on the problem."""
-        torch = self.torch
         self._no_web('grid_problem')
-        self._grid_dropout(dropout, 'grid_problem')
-        self._check_store_capacity(store)
-        self.check_node_counts(store.n, 'grid_problem')
-        G = len(store)
-        if G == 0 or int(np.asarray(store.n).min()) < 1:
-            raise _lib.SiameseHipError('grid_problem: every store graph needs at least one node')
-        q = np.arange(G) if q_idx is None else np.asarray(q_idx, np.int64).reshape(-1)
-        db = np.arange(G) if db_idx is None else np.asarray(db_idx, np.int64).reshape(-1)
-        both = np.concatenate([q, db])
-        if both.size and (both.min() < 0 or both.max() >= G):
-            raise _lib.SiameseHipError('grid_problem: graph ids must lie in [0, {})'.format(G))
-        uniq, inv = np.unique(both, return_inverse=True)
-        m, n, dev = int(q.size), int(db.size), self.device
-        lab = torch.as_tensor(labels if torch.is_tensor(labels) else
-                              np.asarray(labels, np.float32), dtype=torch.float32,
-                              device=dev).contiguous()
-        if tuple(lab.shape) != (m, n):
-            raise _lib.SiameseHipError('grid_problem: labels must be [{}][{}]'.format(m, n))
-        if y_stats is None:
-            y_stats = _label_stats(torch, lab, m * n)
-        E, U = self.embed_dim, int(uniq.size)
-        f32 = dict(dtype=torch.float32, device=dev)
-
-        def ws(nbytes):
-            return torch.empty(nbytes // 4 + 1, **f32)
-        return GridProblem(
-            store_dev=store.to_device(dev), m=m, n=n, labels=lab, y_stats=y_stats,
-            uniq=torch.from_numpy(uniq.astype(np.int32)).to(dev),
-            q_pos=torch.from_numpy(inv[:m].astype(np.int64)).to(dev),
-            db_pos=torch.from_numpy(inv[m:].astype(np.int64)).to(dev),
-            identity=bool(m == n == U and np.array_equal(q, uniq) and np.array_equal(db, uniq)),
-            emb=torch.empty((U, E), **f32), g_emb=torch.empty((U, E), **f32),
-            g_q=torch.empty((m, E), **f32), g_db=torch.empty((n, E), **f32),
-            status=torch.zeros(1, dtype=torch.int32, device=dev),
-            ws_grid=ws((_lib.dot_score_grid_bwd_workspace_bytes if self.is_dot else
-                        _lib.score_grid_bwd_workspace_bytes)(
-                self._sg_keep1() if dropout else self.sg, m, n)),
-            ws_embed=ws(_lib.embed_drop_bwd_workspace_bytes(self.sg, U) if dropout else
-                        _lib.embed_bwd_workspace_bytes(self.sg, U)),
-            dropout=dropout)
+        return self._grid_problem('grid_problem', store, labels, q_idx, db_idx, y_stats, dropout)
 
     def grid_fwd_bwd(self, store, labels=None, q_idx=None, db_idx=None, add_label_term=True,
                      s_out=None, dropout=None, seed=None):
@@ -850,65 +924,19 @@ class SiameseGCNTNMSE(object):
         ordinary dropout of a batched Siamese model and deviates from the reference, which
         draws fresh masks for every pair (quirk A4): the loss and gradient are not those of
         fwd_bwd over the m·n pairs.  At flags.dropout = 0 it equals dropout=None."""
-        if isinstance(store, GridProblem):
-            gp = store
-            if dropout is not None and dropout != gp.dropout:
-                raise _lib.SiameseHipError('grid_fwd_bwd: dropout={!r} on a grid_problem built '
-                                           'with dropout={!r}'.format(dropout, gp.dropout))
-            self._grid_dropout(gp.dropout, 'grid_fwd_bwd')
-        else:
-            self._grid_dropout(dropout, 'grid_fwd_bwd')
-            gp = self.grid_problem(store, labels, q_idx, db_idx, dropout=dropout)
-        sg, nmax = self.sg, self.n_max
-        U = int(gp.uniq.numel())
-        if gp.dropout:
-            seed = self._seed(seed)
-            sg = self._sg_keep1()   # the grid's model: the masks are in the embeddings
-            _lib.embed_drop(self.sg, gp.store_dev, nmax, gp.uniq, U, 0, self.params, seed,
-                            gp.emb, gp.status)
-        else:
-            _lib.embed(sg, gp.store_dev, nmax, gp.uniq, U, self.params, gp.emb, gp.status)
-        eq, edb = (gp.emb, gp.emb) if gp.identity else (gp.emb[gp.q_pos], gp.emb[gp.db_pos])
-        if self.is_dot:   # no variables in the head: the node-stack backward writes all of grad
-            E = int(gp.emb.shape[1])
-            _lib.dot_score_grid_fwd_bwd(sg, eq, E, edb, E, gp.m, gp.n, gp.labels, gp.n,
-                                        gp.m * gp.n, gp.y_stats, add_label_term, s_out, gp.n,
-                                        gp.g_q, gp.g_db, self.loss_buf, gp.ws_grid)
-        else:
-            _lib.score_grid_fwd_bwd(sg, eq, edb, gp.m, gp.n, self.params, gp.labels, gp.n,
-                                    gp.m * gp.n, gp.y_stats, add_label_term, s_out, gp.n, gp.g_q,
-                                    gp.g_db, self.grad, self.loss_buf, gp.ws_grid)
-        if gp.identity:
-            self.torch.add(gp.g_q, gp.g_db, out=gp.g_emb)
-        else:
-            gp.g_emb.zero_()
-            gp.g_emb.index_add_(0, gp.q_pos, gp.g_q)
-            gp.g_emb.index_add_(0, gp.db_pos, gp.g_db)
-        if gp.dropout:
-            _lib.embed_drop_bwd(self.sg, gp.store_dev, nmax, gp.uniq, U, 0, self.params, seed,
-                                gp.g_emb, self.grad, gp.ws_embed, gp.status)
-        else:
-            _lib.embed_bwd(sg, gp.store_dev, nmax, gp.uniq, U, self.params, gp.g_emb,
-                           self.grad, gp.ws_embed, gp.status)
-        return gp
+        if isinstance(store, GridProblem):   # a store is refused by grid_problem, in its place
+            self._no_web('grid_fwd_bwd')
+        return self._grid_fwd_bwd('grid_fwd_bwd', self.grid_problem, store, labels, q_idx,
+                                  db_idx, add_label_term, s_out, dropout, seed)
 
     def grid_train_step(self, store, labels=None, q_idx=None, db_idx=None, sync=True,
                         dropout=None):
         """grid_fwd_bwd followed by Adam: train_step's embed-once counterpart (same loss
         return: loss_mse + weight decay at the pre-update parameters).  With dropout='graph'
         every step draws new masks (the seed follows step_count)."""
-        self.grid_fwd_bwd(store, labels, q_idx, db_idx, dropout=dropout)
-        if self.grad_hook is not None:
-            self.grad_hook(self)
-        self.apply_adam()
-        self.step_count += 1
-        if not sync:
-            return None
-        return float(self.loss_buf[0].item() + self.reg_buf[0].item())
+        return self._grid_train_step(self.grid_fwd_bwd, store, labels, q_idx, db_idx, sync,
+                                     dropout)
 
-    # ---- embed-once training for graph-store models
-    # (include/siamese_web_embed_train.h: dropout 0 only;
-    # include/siamese_web_embed_drop.h: dropout='graph', masks keyed per graph) ----
     def web_grid_problem(self, store, labels, q_idx=None, db_idx=None, y_stats=None,
                          dropout=None):
         """grid_problem for a graph-store (Web) model: the device-resident state of an m x n
@@ -918,50 +946,9 @@ class SiameseGCNTNMSE(object):
         times (web_grid_fwd_bwd / web_grid_train_step).
         dropout: None serves flags.dropout = 0 only; 'graph' trains with dropout masks keyed
         per graph (web_grid_fwd_bwd) and is stored on the problem."""
-        torch = self.torch
         self._only_web('web_grid_problem')
-        self._grid_dropout(dropout, 'web_grid_problem')
-        self.check_node_counts(store.n, 'web_grid_problem')
-        G = len(store)
-        if G == 0 or int(np.asarray(store.n).min()) < 1:
-            raise _lib.SiameseHipError('web_grid_problem: every store graph needs at least one '
-                                       'node')
-        q = np.arange(G) if q_idx is None else np.asarray(q_idx, np.int64).reshape(-1)
-        db = np.arange(G) if db_idx is None else np.asarray(db_idx, np.int64).reshape(-1)
-        both = np.concatenate([q, db])
-        if both.size and (both.min() < 0 or both.max() >= G):
-            raise _lib.SiameseHipError('web_grid_problem: graph ids must lie in [0, {})'.format(G))
-        uniq, inv = np.unique(both, return_inverse=True)
-        m, n, dev = int(q.size), int(db.size), self.device
-        lab = torch.as_tensor(labels if torch.is_tensor(labels) else
-                              np.asarray(labels, np.float32), dtype=torch.float32,
-                              device=dev).contiguous()
-        if tuple(lab.shape) != (m, n):
-            raise _lib.SiameseHipError('web_grid_problem: labels must be [{}][{}]'.format(m, n))
-        if y_stats is None:
-            y_stats = _label_stats(torch, lab, m * n)
-        ld, U = _lib.web_embed_ld(self.sg), int(uniq.size)
-        f32 = dict(dtype=torch.float32, device=dev)
-
-        def ws(nbytes):
-            return torch.empty(nbytes // 4 + 1, **f32)
-        # the gradient buffers start as zeros: the kernels leave columns [D, ld) untouched
-        return GridProblem(
-            store_dev=(store, store.to_device(dev)), m=m, n=n, labels=lab, y_stats=y_stats,
-            uniq=torch.from_numpy(uniq.astype(np.int32)).to(dev),
-            q_pos=torch.from_numpy(inv[:m].astype(np.int64)).to(dev),
-            db_pos=torch.from_numpy(inv[m:].astype(np.int64)).to(dev),
-            identity=bool(m == n == U and np.array_equal(q, uniq) and np.array_equal(db, uniq)),
-            emb=torch.empty((U, ld), **f32), g_emb=torch.zeros((U, ld), **f32),
-            g_q=torch.zeros((m, ld), **f32), g_db=torch.zeros((n, ld), **f32),
-            status=torch.zeros(1, dtype=torch.int32, device=dev),
-            ws_grid=ws(_lib.web_score_grid_bwd_workspace_bytes(
-                self._sg_keep1() if dropout else self.sg, m, n)),
-            ws_embed=ws(_lib.web_embed_drop_bwd_workspace_bytes(self.sg, U) if dropout else
-                        _lib.web_embed_bwd_workspace_bytes(self.sg, U)),
-            ws_fwd=ws(_lib.web_embed_drop_workspace_bytes(self.sg, U) if dropout else
-                      _lib.web_embed_workspace_bytes(self.sg, U)),
-            dropout=dropout)
+        return self._grid_problem('web_grid_problem', store, labels, q_idx, db_idx, y_stats,
+                                  dropout)
 
     def web_grid_fwd_bwd(self, store, labels=None, q_idx=None, db_idx=None, add_label_term=True,
                          s_out=None, dropout=None, seed=None):
@@ -985,45 +972,8 @@ class SiameseGCNTNMSE(object):
         reference's per-pair masks (quirk A4), so the loss and gradient are not those of
         fwd_bwd over the m·n pairs.  At flags.dropout = 0 it equals dropout=None."""
         self._only_web('web_grid_fwd_bwd')
-        if isinstance(store, GridProblem):
-            gp = store
-            if dropout is not None and dropout != gp.dropout:
-                raise _lib.SiameseHipError('web_grid_fwd_bwd: dropout={!r} on a web_grid_problem '
-                                           'built with dropout={!r}'.format(dropout, gp.dropout))
-            self._grid_dropout(gp.dropout, 'web_grid_fwd_bwd')
-        else:
-            self._grid_dropout(dropout, 'web_grid_fwd_bwd')
-            gp = self.web_grid_problem(store, labels, q_idx, db_idx, dropout=dropout)
-        if gp.ws_fwd is None:
-            raise _lib.SiameseHipError('web_grid_fwd_bwd: the problem was built by grid_problem; '
-                                       'use web_grid_problem')
-        sg, csr = self.sg, gp.store_dev[1]
-        U, ld = int(gp.uniq.numel()), int(gp.emb.shape[1])
-        if gp.dropout:
-            seed = self._seed(seed)
-            sg = self._sg_keep1()   # the grid's model: the masks are in the embeddings
-            _lib.web_embed_drop(self.sg, csr, gp.uniq, U, 0, self.params, seed, gp.emb,
-                                gp.ws_fwd, gp.status)
-        else:
-            _lib.web_embed(sg, csr, gp.uniq, U, self.params, gp.emb, gp.ws_fwd, gp.status)
-        eq, edb = (gp.emb, gp.emb) if gp.identity else (gp.emb[gp.q_pos], gp.emb[gp.db_pos])
-        _lib.web_score_grid_fwd_bwd(sg, eq, ld, edb, ld, gp.m, gp.n, self.params, gp.labels,
-                                    gp.n, gp.m * gp.n, gp.y_stats, add_label_term, s_out, gp.n,
-                                    gp.g_q, ld, gp.g_db, ld, self.grad, self.loss_buf,
-                                    gp.ws_grid)
-        if gp.identity:
-            self.torch.add(gp.g_q, gp.g_db, out=gp.g_emb)
-        else:
-            gp.g_emb.zero_()
-            gp.g_emb.index_add_(0, gp.q_pos, gp.g_q)
-            gp.g_emb.index_add_(0, gp.db_pos, gp.g_db)
-        if gp.dropout:
-            _lib.web_embed_drop_bwd(self.sg, csr, gp.uniq, U, 0, self.params, seed, gp.g_emb, ld,
-                                    self.grad, gp.ws_embed, gp.status)
-        else:
-            _lib.web_embed_bwd(sg, csr, gp.uniq, U, self.params, gp.g_emb, ld, self.grad,
-                               gp.ws_embed, gp.status)
-        return gp
+        return self._grid_fwd_bwd('web_grid_fwd_bwd', self.web_grid_problem, store, labels,
+                                  q_idx, db_idx, add_label_term, s_out, dropout, seed)
 
     def web_grid_train_step(self, store, labels=None, q_idx=None, db_idx=None, sync=True,
                             dropout=None):
@@ -1031,14 +981,8 @@ class SiameseGCNTNMSE(object):
         graph-store models (same loss return: loss_mse + weight decay at the pre-update
         parameters).  With dropout='graph' every step draws new masks (the seed follows
         step_count)."""
-        self.web_grid_fwd_bwd(store, labels, q_idx, db_idx, dropout=dropout)
-        if self.grad_hook is not None:
-            self.grad_hook(self)
-        self.apply_adam()
-        self.step_count += 1
-        if not sync:
-            return None
-        return float(self.loss_buf[0].item() + self.reg_buf[0].item())
+        return self._grid_train_step(self.web_grid_fwd_bwd, store, labels, q_idx, db_idx, sync,
+                                     dropout)
 
     def flat_params(self) -> np.ndarray:
         return self.params.detach().cpu().numpy()

@@ -20,11 +20,11 @@ pair_offset, exactly like the record path's keys.
 """
 from __future__ import annotations
 
-import weakref
 from typing import Optional, Sequence
 
 import numpy as np
 
+from .allpairs import AllPairsGrid
 from .shard import shard_range
 
 
@@ -170,7 +170,7 @@ class WebAllPairs(object):
                                batch_total=self.total, y_stats=self.y_stats, chunk=self.chunk)
 
 
-class WebAllPairsGrid(object):
+class WebAllPairsGrid(AllPairsGrid):
     """The all-pairs step embed-once on the graph store: allpairs.AllPairsGrid's counterpart
     for model.web_grid_fwd_bwd (dropout=None: flags.dropout = 0 only; dropout='graph': one
     dropout mask set per graph per step).  gs: a GraphSet, whose CsrStore is built the way
@@ -180,35 +180,10 @@ class WebAllPairsGrid(object):
     (include/siamese_web_embed_train.h, include/siamese_web_embed_drop.h).  Same loss and
     gradient as WebAllPairs' batch through fwd_bwd at dropout 0, up to fp32 summation order."""
 
+    API = 'web_grid_'
+
     def __init__(self, gs, labels: np.ndarray, device='cuda', dropout=None,
                  d_in: Optional[int] = None, n_cap: Optional[int] = None):
-        import torch
-        self.store = gs if isinstance(gs, CsrStore) else CsrStore(
+        store = gs if isinstance(gs, CsrStore) else CsrStore(
             gs.mgs, d_in if d_in is not None else gs.d_in, n_cap)
-        G = len(self.store)
-        lab = np.ascontiguousarray(np.asarray(labels, np.float32).reshape(G, G))
-        self.total = G * G
-        self.labels = torch.from_numpy(lab).to(device)
-        y = lab.reshape(-1).astype(np.float64)
-        ybar = y.mean() if y.size else 0.0
-        self.y_stats = torch.tensor([ybar, 0.5 * ((y - ybar) ** 2).sum()], dtype=torch.float32,
-                                    device=device)
-        self.dropout = dropout
-        self._problem = None
-        self._owner = None
-
-    def problem(self, model):
-        """The model's web_grid_problem of this grid (built once per model)."""
-        owner = self._owner() if self._owner is not None else None
-        if owner is not model:
-            self._problem = model.web_grid_problem(self.store, self.labels,
-                                                   y_stats=self.y_stats, dropout=self.dropout)
-            self._owner = weakref.ref(model)
-        return self._problem
-
-    def fwd_bwd(self, model, add_label_term: bool = True):
-        """Leaves the gradient / loss_mse in model.grad / model.loss_buf."""
-        model.web_grid_fwd_bwd(self.problem(model), add_label_term=add_label_term)
-
-    def train_step(self, model, sync: bool = True):
-        return model.web_grid_train_step(self.problem(model), sync=sync)
+        self._setup(store, labels, device, dropout)
