@@ -304,6 +304,14 @@ def lib():
         L.sg_ged_exact_grid.argtypes = [vp, vp, vp, c_i32, c_i32, vp, c_i64, vp, c_i64, c_i64,
                                         vp, c_i64, vp, vp, vp, vp, vp, vp]
         L.sg_ged_exact_grid.restype = c_i32
+    # beam-search graph edit distance (include/siamese_ged_beam.h); a library without it
+    # still loads
+    if all(hasattr(L, s) for s in GED_BEAM_SYMBOLS):
+        L.sg_ged_beam_grid_workspace_bytes.argtypes = [c_i64, c_i64, c_i32]
+        L.sg_ged_beam_grid_workspace_bytes.restype = c_i64
+        L.sg_ged_beam_grid.argtypes = [vp, vp, vp, c_i32, c_i32, vp, c_i64, vp, c_i64, c_i32,
+                                       vp, c_i64, vp, vp, vp, vp, vp, vp]
+        L.sg_ged_beam_grid.restype = c_i32
     _lib = L
     return L
 
@@ -378,6 +386,12 @@ GED_SYMBOLS = ('sg_ged_grid_workspace_bytes', 'sg_ged_grid')
 # budget: a branch and bound per pair seeded with the bipartite bounds; detected by presence)
 GED_EXACT_SYMBOLS = ('sg_ged_exact_grid_workspace_bytes', 'sg_ged_exact_grid')
 GED_EXACT_MAX_BUDGET = 1 << 24
+
+# the symbols of include/siamese_ged_beam.h (beam-search graph edit distance: a level-synchronous
+# beam per pair seeded with the bipartite bounds, for all graphs of the store; detected by
+# presence)
+GED_BEAM_SYMBOLS = ('sg_ged_beam_grid_workspace_bytes', 'sg_ged_beam_grid')
+GED_BEAM_MAX_WIDTH = 128
 
 # class_start entries of sg_pair_order_cls (include/siamese_hip.h SG_FAST_CLASSES_P1)
 FAST_CLASSES_P1 = 5
@@ -870,6 +884,7 @@ _dot_fn = functools.partial(_optional_fn, header='siamese_dot_embed.h')
 _eval_fn = functools.partial(_optional_fn, header='siamese_eval.h')
 _ged_fn = functools.partial(_optional_fn, header='siamese_ged.h')
 _ged_exact_fn = functools.partial(_optional_fn, header='siamese_ged_exact.h')
+_ged_beam_fn = functools.partial(_optional_fn, header='siamese_ged_beam.h')
 
 
 def web_embed_drop_workspace_bytes(m: SgModel, count: int) -> int:
@@ -1047,6 +1062,29 @@ def ged_exact_grid(store_dev, n_max, q_idx, n_q, db_idx, n_db, max_expansions, u
         _ptr(db_idx), int(n_db), int(max_expansions), _ptr(ub_out), int(ld), _ptr(lb_out),
         _ptr(map_out), _ptr(expansions_out), _ptr(status), _ptr(workspace), _stream(stream)),
         'sg_ged_exact_grid')
+
+
+def ged_beam_grid_workspace_bytes(n_q: int, n_db: int, n_max: int) -> int:
+    b = int(_ged_beam_fn('sg_ged_beam_grid_workspace_bytes')(int(n_q), int(n_db), int(n_max)))
+    if b < 0:
+        raise SiameseHipError('sg_ged_beam_grid_workspace_bytes: the call serves stores of '
+                              '1 <= n_max <= 32 and grids of at most 2^24 rows, 2^24 columns '
+                              'and 2^32 pairs')
+    return b
+
+
+def ged_beam_grid(store_dev, n_max, q_idx, n_q, db_idx, n_db, width, ub_out, ld, lb_out,
+                  map_out=None, expanded_out=None, status=None, workspace=None, stream=None):
+    """sg_ged_beam_grid over a device dense store (adj, types, n) = GraphStore.to_device():
+    ub_out / lb_out int32 [n_q] rows of stride ld (lb == ub: proven), optionally the map of the
+    path that costs ub (int8 [n_q][n_db][n_max]) and the states expanded (int32, stride ld);
+    q_idx / db_idx int32 device tensors or None."""
+    adj, types, n = store_dev
+    check(_ged_beam_fn('sg_ged_beam_grid')(
+        _ptr(adj), _ptr(types), _ptr(n), int(n.numel()), int(n_max), _ptr(q_idx), int(n_q),
+        _ptr(db_idx), int(n_db), int(width), _ptr(ub_out), int(ld), _ptr(lb_out),
+        _ptr(map_out), _ptr(expanded_out), _ptr(status), _ptr(workspace), _stream(stream)),
+        'sg_ged_beam_grid')
 
 
 def seed_advance(seed_dev, delta=1, stream=None):

@@ -92,10 +92,14 @@ def load_graph_set(name: str = 'syn_aids700nef', n_max: int = 10, seed: int = 12
     ged='bp': the bipartite upper bounds of the graphs themselves, computed on `device`
     (graphembedding_amd.ged.ged_matrix; needs the store); ged='exact': the budgeted branch and
     bound's ub at ged.GED_EXACT_DEFAULT_BUDGET expansions per pair, the exact distance wherever
-    it is proven (the count of unproven pairs is logged)."""
-    if ged not in ('synthetic', 'bp', 'exact'):
+    it is proven (the count of unproven pairs is logged); ged='lbeam<w>' (w in [1, 128], e.g.
+    'lbeam80'): the level-synchronous beam search's ub at width w (ged.beam_label_matrix), for
+    every graph of the store."""
+    from .ged import beam_width_of
+    beam = beam_width_of(ged)
+    if ged not in ('synthetic', 'bp', 'exact') and beam is None:
         raise RuntimeError('Unknown ged labels {}'.format(ged))
-    if ged in ('bp', 'exact') and not with_store:
+    if (ged in ('bp', 'exact') or beam is not None) and not with_store:
         raise RuntimeError("ged={!r} computes from the dense store: with_store=True is "
                            "needed".format(ged))
     tr, te = synthetic_graphs(name, seed)
@@ -111,6 +115,9 @@ def load_graph_set(name: str = 'syn_aids700nef', n_max: int = 10, seed: int = 12
     elif ged == 'exact':
         from .ged import exact_label_matrix
         dmat = exact_label_matrix(store, device=device)
+    elif beam is not None:
+        from .ged import beam_label_matrix
+        dmat = beam_label_matrix(store, width=beam, device=device)
     else:
         dmat = synthetic_ged_matrix(graphs)
     return GraphSet(graphs=graphs, mgs=mgs, d_in=enc.input_dim(), n_max=n_max, store=store,

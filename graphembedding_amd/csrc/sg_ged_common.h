@@ -1,6 +1,7 @@
 // sg_ged_common.h — what the graph edit distance units share (sg_ged.hip: the bipartite
-// bounds of include/siamese_ged.h; sg_ged_exact.hip: the budgeted search of
-// include/siamese_ged_exact.h that those bounds seed): the workspace entry of a graph and the
+// bounds of include/siamese_ged.h; sg_ged_exact.hip and sg_ged_beam.hip: the budgeted search of
+// include/siamese_ged_exact.h and the beam search of include/siamese_ged_beam.h that those
+// bounds seed): the workspace entry of a graph and the
 // kernel that builds it, the wave-wide assignment solver and the cost of the edit path an
 // assignment induces, and the rules on m, n and n_max.
 #pragma once

@@ -3,10 +3,11 @@
 Only `normalized_dist` (distance.py:59-60) is on the hot path.  `ged` and `mcs`
 shell out to the Java graph-matching-toolkit / the `chorus` library in the
 reference (distance.py:10-56); those solvers are out of scope here and raise
-unless a cached distance exists (see dist_calculator.DistCalculator).  Two
+unless a cached distance exists (see dist_calculator.DistCalculator).  Three
 algorithms are computed here, on the device (graphembedding_amd.ged): 'bp', the
-bipartite upper bound (include/siamese_ged.h), and 'exact', the budgeted branch
-and bound seeded with it (include/siamese_ged_exact.h).
+bipartite upper bound (include/siamese_ged.h), 'exact', the budgeted branch
+and bound seeded with it (include/siamese_ged_exact.h), and 'lbeam<w>', the
+level-synchronous beam search seeded with it (include/siamese_ged_beam.h).
 """
 from __future__ import annotations
 
@@ -27,10 +28,22 @@ def ged(g1, g2, algo, debug=False, timeit=False):
     (more than 16 nodes, or the budget spent) raises with the bounds it has.  The name is not
     'astar': the value is the same distance, the program is not the toolkit's.
 
-    Every other algo raises: the toolkit's A* and beam search are out of scope."""
+    algo='lbeam<w>' (w in [1, 128], e.g. 'lbeam80'): the upper bound of the level-synchronous
+    beam search of width w (include/siamese_ged_beam.h), seeded with 'bp' and never above it,
+    for graphs of at most 32 nodes; a width outside [1, 128] raises.  The name is not
+    'beam<w>': the toolkit's beam search is best-first over a truncated OPEN list, this one
+    keeps the w best states of every level, so its values are not claimed to be the toolkit's.
+
+    Every other algo raises: the toolkit's own A*, beam search ('beam80'), 'hungarian' and 'vj'
+    are out of scope."""
     if algo == 'bp':
         from .ged import ged_pair
         return ged_pair(g1, g2)[0]
+    if isinstance(algo, str) and algo.startswith('lbeam'):
+        from .ged import beam_width_of, ged_pair
+        w = beam_width_of(algo)
+        if w is not None:
+            return ged_pair(g1, g2, beam_width=w)[0]
     if algo == 'exact':
         from .ged import GED_EXACT_DEFAULT_BUDGET, ged_pair
         ub, lb = ged_pair(g1, g2, exact_budget=GED_EXACT_DEFAULT_BUDGET)

@@ -11,6 +11,11 @@ With exact_budget the calls go through include/siamese_ged_exact.h instead: a de
 and bound per pair, seeded with those bounds and cut off after exact_budget expansions.  It
 proves the distance (lb == ub) where it finishes, which it does on graphs of at most about 10
 nodes, and tightens ub elsewhere; graphs of more than 16 nodes keep the bipartite bounds.
+
+With beam_width the calls go through include/siamese_ged_beam.h: a level-synchronous beam of at
+most beam_width states per pair, seeded with the same bounds, for every graph of the store (no
+16-node limit).  It tightens ub, and proves the distance (lb == ub) where the width never cut a
+level.  It is not the graph-matching-toolkit's beam search and does not claim its values.
 """
 from __future__ import annotations
 
@@ -21,6 +26,7 @@ from . import _lib
 GED_MAX_NODES = 32
 GED_EXACT_MAX_NODES = 16             # larger graphs keep the bipartite bounds
 GED_EXACT_DEFAULT_BUDGET = 1 << 20   # expansions per pair of distance.ged(..., 'exact')
+GED_BEAM_DEFAULT_WIDTH = 80          # states per level of beam_label_matrix
 
 
 def _index(idx, device):
@@ -31,7 +37,8 @@ def _index(idx, device):
 
 
 def ged_grid(store, q_idx=None, db_idx=None, both_orders=True, bounds=False, mapping=False,
-             device='cuda', ld=None, return_status=False, exact_budget=None, expansions=False):
+             device='cuda', ld=None, return_status=False, exact_budget=None, expansions=False,
+             beam_width=None, expanded=False):
     """Bipartite GED bounds of store graphs q_idx x db_idx (None: every graph of the store).
 
     Returns the upper bound ub as a device int32 tensor [m][n] (min over both assignment
@@ -44,13 +51,25 @@ def ged_grid(store, q_idx=None, db_idx=None, both_orders=True, bounds=False, map
     exact_budget=B (an int in [0, 2^24]) runs the budgeted branch and bound on every pair: ub is
     the cost of the best edit path found (never above the bipartite one), lb equals ub where the
     distance is proven, the mapping is that path's, and expansions=True additionally returns the
-    int64 tensor [m][n] of expansions spent (after the mapping, before the status)."""
+    int64 tensor [m][n] of expansions spent (after the mapping, before the status).
+
+    beam_width=w (an int in [0, 128]; not together with exact_budget) runs the level-synchronous
+    beam on every pair instead and returns (ub, lb, ...) in the same way: lb equals ub where the
+    beam was never truncated, and expanded=True additionally returns the int32 tensor [m][n] of
+    states expanded, in the place expansions takes."""
     import torch
     exact = exact_budget is not None
+    beam = beam_width is not None
+    if exact and beam:
+        raise ValueError('exact_budget and beam_width are mutually exclusive')
     if expansions and not exact:
         raise ValueError('expansions are counted by the exact search: pass exact_budget')
+    if expanded and not beam:
+        raise ValueError('expanded states are counted by the beam search: pass beam_width')
     if exact and not both_orders:
         raise ValueError('the exact search is seeded with both assignment orders')
+    if beam and not both_orders:
+        raise ValueError('the beam search is seeded with both assignment orders')
     adj, types, n_nodes = store.to_device(device)
     G = int(n_nodes.numel())
     dev = adj.device
@@ -61,16 +80,22 @@ def ged_grid(store, q_idx=None, db_idx=None, both_orders=True, bounds=False, map
     if ld < n:
         raise ValueError('ld {} below n {}'.format(ld, n))
     nbytes = (_lib.ged_exact_grid_workspace_bytes if exact else
+              _lib.ged_beam_grid_workspace_bytes if beam else
               _lib.ged_grid_workspace_bytes)(m, n, store.n_max)
     ws = torch.empty(nbytes // 4 + 1, dtype=torch.int32, device=dev)
     ub = torch.empty((m, ld), dtype=torch.int32, device=dev)
-    lb = torch.empty((m, ld), dtype=torch.int32, device=dev) if bounds or exact else None
+    lb = torch.empty((m, ld), dtype=torch.int32, device=dev) if bounds or exact or beam else None
     mp = torch.empty((m, n, store.n_max), dtype=torch.int8, device=dev) if mapping else None
     ex = torch.empty((m, ld), dtype=torch.int64, device=dev) if expansions else None
+    if expanded:
+        ex = torch.empty((m, ld), dtype=torch.int32, device=dev)
     status = torch.zeros(1, dtype=torch.int32, device=dev)
     if exact:
         _lib.ged_exact_grid((adj, types, n_nodes), store.n_max, q, m, db, n, int(exact_budget),
                             ub, ld, lb, mp, ex, status, ws)
+    elif beam:
+        _lib.ged_beam_grid((adj, types, n_nodes), store.n_max, q, m, db, n, int(beam_width),
+                           ub, ld, lb, mp, ex, status, ws)
     else:
         _lib.ged_grid((adj, types, n_nodes), store.n_max, q, m, db, n, both_orders, ub, ld, lb,
                       mp, status, ws)
@@ -79,14 +104,15 @@ def ged_grid(store, q_idx=None, db_idx=None, both_orders=True, bounds=False, map
         if rc != 0:
             raise _lib.SiameseHipError('{}: {} (a graph id outside the store, or a '
                                        'node count outside [1, n_max])'.format(
-                                           'sg_ged_exact_grid' if exact else 'sg_ged_grid',
+                                           'sg_ged_exact_grid' if exact else
+                                           'sg_ged_beam_grid' if beam else 'sg_ged_grid',
                                            _lib._ERR_NAMES.get(rc, rc)))
     out = [ub[:, :n]]
     if bounds:
         out.append(lb[:, :n])
     if mapping:
         out.append(mp)
-    if expansions:
+    if expansions or expanded:
         out.append(ex[:, :n])
     if return_status:
         out.append(status)
@@ -133,29 +159,31 @@ def _attr(g, name):
 
 
 def ged_matrix(graphs_or_store, both_orders=True, device='cuda', node_feat_name='type',
-               exact_budget=None):
+               exact_budget=None, beam_width=None):
     """All-pairs upper bounds as a host int64 matrix [G][G], ready for
     DistCalculator.from_matrix.  With both_orders it is symmetric with a zero diagonal.
     With exact_budget=B: (matrix, proven), the budgeted search's ub and the bool matrix of the
-    pairs whose distance it proved (ub is the exact distance there)."""
+    pairs whose distance it proved (ub is the exact distance there); with beam_width=w the
+    same pair from the beam search."""
     store = graphs_or_store
     if not hasattr(store, 'to_device'):
         store = store_of_graphs(graphs_or_store, node_feat_name)
-    if exact_budget is not None:
+    if exact_budget is not None or beam_width is not None:
         ub, lb = ged_grid(store, both_orders=both_orders, bounds=True, device=device,
-                          exact_budget=exact_budget)
+                          exact_budget=exact_budget, beam_width=beam_width)
         ub, lb = ub.cpu().numpy().astype(np.int64), lb.cpu().numpy().astype(np.int64)
         return ub, ub == lb
     ub = ged_grid(store, both_orders=both_orders, device=device)
     return ub.cpu().numpy().astype(np.int64)
 
 
-def ged_pair(g1, g2, device='cuda', node_feat_name='type', exact_budget=None):
+def ged_pair(g1, g2, device='cuda', node_feat_name='type', exact_budget=None, beam_width=None):
     """(ub, lb) of two networkx graphs through a two-graph store, ub the min over both
-    assignment orders; with exact_budget=B those of the budgeted search (ub == lb: proven)."""
+    assignment orders; with exact_budget=B those of the budgeted search (ub == lb: proven),
+    with beam_width=w those of the beam search."""
     store = store_of_graphs([g1, g2], node_feat_name)
     ub, lb = ged_grid(store, [0], [1], both_orders=True, bounds=True, device=device,
-                      exact_budget=exact_budget)
+                      exact_budget=exact_budget, beam_width=beam_width)
     return int(ub.item()), int(lb.item())
 
 
@@ -171,3 +199,30 @@ def exact_label_matrix(graphs_or_store, device='cuda', node_feat_name='type',
         'exact GED labels: %d of %d pairs left unproven within %d expansions',
         int((~proven).sum()), proven.size, budget)
     return dmat
+
+
+def beam_label_matrix(graphs_or_store, width=GED_BEAM_DEFAULT_WIDTH, device='cuda',
+                      node_feat_name='type'):
+    """The label matrix of ged='lbeam<w>' / ged_labels='lbeam<w>': the beam search's ub for all
+    pairs, with the number of pairs left unproven logged (their ub is the best path found)."""
+    import logging
+    dmat, proven = ged_matrix(graphs_or_store, device=device, node_feat_name=node_feat_name,
+                              beam_width=width)
+    logging.getLogger(__name__).info(
+        'beam GED labels: %d of %d pairs left unproven at width %d',
+        int((~proven).sum()), proven.size, width)
+    return dmat
+
+
+def beam_width_of(name):
+    """The width w of an algorithm / label name 'lbeam<w>' (w in [1, 128]), or None for any
+    other name; a width outside the range raises."""
+    import re
+    mt = re.fullmatch(r'lbeam(\d+)', name) if isinstance(name, str) else None
+    if mt is None:
+        return None
+    w = int(mt.group(1))
+    if not 1 <= w <= _lib.GED_BEAM_MAX_WIDTH:
+        raise RuntimeError('{!r}: the beam width is in [1, {}]'.format(
+            name, _lib.GED_BEAM_MAX_WIDTH))
+    return w

@@ -202,7 +202,12 @@ def main(flags=None, device='cuda', return_objects=False):
         elif f.ged_labels == 'synthetic':
             dmat = synthetic_ged_matrix(gs)
         else:
-            raise RuntimeError('Unknown ged_labels {}'.format(f.ged_labels))
+            from .ged import beam_label_matrix, beam_width_of
+            beam = beam_width_of(f.ged_labels)   # 'lbeam<w>': the beam search's ub
+            if beam is None:
+                raise RuntimeError('Unknown ged_labels {}'.format(f.ged_labels))
+            dmat = beam_label_matrix(gs, width=beam, device=device,
+                                     node_feat_name=f.node_feat_name)
         dc = DistCalculator.from_matrix(f.dataset, gs, dmat, f.dist_metric, f.dist_algo)
     else:
         dc = DistCalculator(f.dataset, f.dist_metric, f.dist_algo)
