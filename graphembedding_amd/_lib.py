@@ -312,6 +312,14 @@ def lib():
         L.sg_ged_beam_grid.argtypes = [vp, vp, vp, c_i32, c_i32, vp, c_i64, vp, c_i64, c_i32,
                                        vp, c_i64, vp, vp, vp, vp, vp, vp]
         L.sg_ged_beam_grid.restype = c_i32
+    # bipartite graph edit distance bounds for graph-store (CSR) graphs
+    # (include/siamese_ged_csr.h); a library without them still loads
+    if all(hasattr(L, s) for s in GED_CSR_SYMBOLS):
+        L.sg_csr_ged_grid_workspace_bytes.argtypes = [c_i64, c_i64, c_i32]
+        L.sg_csr_ged_grid_workspace_bytes.restype = c_i64
+        L.sg_csr_ged_grid.argtypes = [ctypes.POINTER(SgCsrStore), vp, c_i64, vp, c_i64, c_i32, vp,
+                                      c_i64, vp, vp, vp, vp, vp]
+        L.sg_csr_ged_grid.restype = c_i32
     _lib = L
     return L
 
@@ -392,6 +400,11 @@ GED_EXACT_MAX_BUDGET = 1 << 24
 # presence)
 GED_BEAM_SYMBOLS = ('sg_ged_beam_grid_workspace_bytes', 'sg_ged_beam_grid')
 GED_BEAM_MAX_WIDTH = 128
+
+# the symbols of include/siamese_ged_csr.h (the bipartite bounds for graph-store (CSR) graphs of
+# up to 512 nodes; detected by presence)
+GED_CSR_SYMBOLS = ('sg_csr_ged_grid_workspace_bytes', 'sg_csr_ged_grid')
+GED_CSR_MAX_NODES = 512
 
 # class_start entries of sg_pair_order_cls (include/siamese_hip.h SG_FAST_CLASSES_P1)
 FAST_CLASSES_P1 = 5
@@ -885,6 +898,7 @@ _eval_fn = functools.partial(_optional_fn, header='siamese_eval.h')
 _ged_fn = functools.partial(_optional_fn, header='siamese_ged.h')
 _ged_exact_fn = functools.partial(_optional_fn, header='siamese_ged_exact.h')
 _ged_beam_fn = functools.partial(_optional_fn, header='siamese_ged_beam.h')
+_ged_csr_fn = functools.partial(_optional_fn, header='siamese_ged_csr.h')
 
 
 def web_embed_drop_workspace_bytes(m: SgModel, count: int) -> int:
@@ -1085,6 +1099,27 @@ def ged_beam_grid(store_dev, n_max, q_idx, n_q, db_idx, n_db, width, ub_out, ld,
         _ptr(db_idx), int(n_db), int(width), _ptr(ub_out), int(ld), _ptr(lb_out),
         _ptr(map_out), _ptr(expanded_out), _ptr(status), _ptr(workspace), _stream(stream)),
         'sg_ged_beam_grid')
+
+
+def csr_ged_grid_workspace_bytes(n_q: int, n_db: int, n_max: int) -> int:
+    b = int(_ged_csr_fn('sg_csr_ged_grid_workspace_bytes')(int(n_q), int(n_db), int(n_max)))
+    if b < 0:
+        raise SiameseHipError('sg_csr_ged_grid_workspace_bytes: the bipartite bounds serve graph '
+                              'stores of 1 <= n_max <= 512 and grids of at most 2^24 rows, 2^24 '
+                              'columns and 2^32 pairs')
+    return b
+
+
+def csr_ged_grid(store: SgCsrStore, q_idx, n_q, db_idx, n_db, both_orders, ub_out, ld,
+                 lb_out=None, map_out=None, status=None, workspace=None, stream=None):
+    """sg_csr_ged_grid over a CSR store struct (CsrStore.to_device()): the bipartite upper bound
+    ub_out int32 [n_q] rows of stride ld, and optionally the lower bound lb_out (same shape) and
+    the 1->2 assignment map_out int16 [n_q][n_db][store.n_max]; q_idx / db_idx int32 device
+    tensors or None (graphs 0 .. n_q-1 / 0 .. n_db-1)."""
+    check(_ged_csr_fn('sg_csr_ged_grid')(
+        ctypes.byref(store), _ptr(q_idx), int(n_q), _ptr(db_idx), int(n_db),
+        int(bool(both_orders)), _ptr(ub_out), int(ld), _ptr(lb_out), _ptr(map_out), _ptr(status),
+        _ptr(workspace), _stream(stream)), 'sg_csr_ged_grid')
 
 
 def seed_advance(seed_dev, delta=1, stream=None):

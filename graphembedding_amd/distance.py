@@ -5,7 +5,8 @@ shell out to the Java graph-matching-toolkit / the `chorus` library in the
 reference (distance.py:10-56); those solvers are out of scope here and raise
 unless a cached distance exists (see dist_calculator.DistCalculator).  Three
 algorithms are computed here, on the device (graphembedding_amd.ged): 'bp', the
-bipartite upper bound (include/siamese_ged.h), 'exact', the budgeted branch
+bipartite upper bound (include/siamese_ged.h; include/siamese_ged_csr.h for graphs
+of 33 to 512 nodes), 'exact', the budgeted branch
 and bound seeded with it (include/siamese_ged_exact.h), and 'lbeam<w>', the
 level-synchronous beam search seeded with it (include/siamese_ged_beam.h).
 """
@@ -19,9 +20,11 @@ def normalized_dist(d, g1, g2):
 def ged(g1, g2, algo, debug=False, timeit=False):
     """algo='bp': the bipartite (Riesen & Bunke) upper bound under the toolkit's AIDS cost
     model, the smaller of both assignment orders (the reference's `_revtakemin` caches), for
-    graphs of at most 32 nodes.  The name is deliberately not 'hungarian': that the toolkit's
-    Hungarian mode builds the same cost matrix (node costs plus local degree differences) and
-    breaks ties the same way has not been checked, so its values are not claimed.
+    graphs of at most 512 nodes (above 32 nodes through the graph-store call of
+    include/siamese_ged_csr.h, same construction and tie rules).  The name is deliberately
+    not 'hungarian': that the toolkit's Hungarian mode builds the same cost matrix (node costs
+    plus local degree differences) and breaks ties the same way has not been checked, so its
+    values are not claimed.
 
     algo='exact': the exact distance under the same cost model, proven by the budgeted branch
     and bound within ged.GED_EXACT_DEFAULT_BUDGET = 2^20 expansions; a pair it cannot prove

@@ -5,7 +5,9 @@ bound of the same construction.
 Cost model (the graph-matching-toolkit's for the AIDS sets, doubled at alpha = 0.5): node
 insertion / deletion 1, node substitution 0 for equal `type` and 1 otherwise, edge insertion /
 deletion 1, edge substitution 0.  lb <= GED <= ub; where lb == ub the distance is exact.  The
-store serves graphs of at most 32 nodes (capacities 10 and 32).
+dense store serves graphs of at most 32 nodes (capacities 10 and 32); a graph store (web.CsrStore,
+csr_store_of_graphs) serves graphs of at most 512 nodes through include/siamese_ged_csr.h, with
+the same construction and tie rules, bounds only.
 
 With exact_budget the calls go through include/siamese_ged_exact.h instead: a depth-first branch
 and bound per pair, seeded with those bounds and cut off after exact_budget expansions.  It
@@ -24,6 +26,7 @@ import numpy as np
 from . import _lib
 
 GED_MAX_NODES = 32
+GED_CSR_MAX_NODES = 512              # graph-store (CSR) graphs: the bipartite bounds only
 GED_EXACT_MAX_NODES = 16             # larger graphs keep the bipartite bounds
 GED_EXACT_DEFAULT_BUDGET = 1 << 20   # expansions per pair of distance.ged(..., 'exact')
 GED_BEAM_DEFAULT_WIDTH = 80          # states per level of beam_label_matrix
@@ -56,8 +59,18 @@ def ged_grid(store, q_idx=None, db_idx=None, both_orders=True, bounds=False, map
     beam_width=w (an int in [0, 128]; not together with exact_budget) runs the level-synchronous
     beam on every pair instead and returns (ub, lb, ...) in the same way: lb equals ub where the
     beam was never truncated, and expanded=True additionally returns the int32 tensor [m][n] of
-    states expanded, in the place expansions takes."""
+    states expanded, in the place expansions takes.
+
+    A graph store (web.CsrStore) goes through sg_csr_ged_grid: the same bounds for graphs of at
+    most 512 nodes, the mapping an int16 tensor; exact_budget and beam_width raise ValueError
+    there."""
     import torch
+    if _is_csr(store):
+        if exact_budget is not None or beam_width is not None or expansions or expanded:
+            raise ValueError('a graph store (CSR) has the bipartite bounds only: no exact_budget, '
+                             'no beam_width')
+        return _csr_ged_grid(store, q_idx, db_idx, both_orders, bounds, mapping, device, ld,
+                             return_status)
     exact = exact_budget is not None
     beam = beam_width is not None
     if exact and beam:
@@ -119,6 +132,47 @@ def ged_grid(store, q_idx=None, db_idx=None, both_orders=True, bounds=False, map
     return out[0] if len(out) == 1 else tuple(out)
 
 
+def _is_csr(store):
+    from .web import CsrStore
+    return isinstance(store, CsrStore)
+
+
+def _csr_ged_grid(store, q_idx, db_idx, both_orders, bounds, mapping, device, ld, return_status):
+    import torch
+    dev = torch.device(device)
+    if dev.type == 'cuda' and dev.index is None:
+        dev = torch.device('cuda', torch.cuda.current_device())
+    struct = store.to_device(dev)
+    G = len(store)
+    q, db = _index(q_idx, dev), _index(db_idx, dev)
+    m = G if q is None else int(q.numel())
+    n = G if db is None else int(db.numel())
+    ld = n if ld is None else int(ld)
+    if ld < n:
+        raise ValueError('ld {} below n {}'.format(ld, n))
+    nbytes = _lib.csr_ged_grid_workspace_bytes(m, n, store.n_max)
+    ws = torch.empty(nbytes // 4 + 1, dtype=torch.int32, device=dev)
+    ub = torch.empty((m, ld), dtype=torch.int32, device=dev)
+    lb = torch.empty((m, ld), dtype=torch.int32, device=dev) if bounds else None
+    mp = torch.empty((m, n, store.n_max), dtype=torch.int16, device=dev) if mapping else None
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    _lib.csr_ged_grid(struct, q, m, db, n, both_orders, ub, ld, lb, mp, status, ws)
+    if not return_status:
+        rc = int(status.item())
+        if rc != 0:
+            raise _lib.SiameseHipError('sg_csr_ged_grid: {} (a graph id outside the store, or a '
+                                       'node count outside [1, n_max])'.format(
+                                           _lib._ERR_NAMES.get(rc, rc)))
+    out = [ub[:, :n]]
+    if bounds:
+        out.append(lb[:, :n])
+    if mapping:
+        out.append(mp)
+    if return_status:
+        out.append(status)
+    return out[0] if len(out) == 1 else tuple(out)
+
+
 class _ConstantEncoder(object):
     """Graphs without the node feature: one type."""
 
@@ -129,13 +183,8 @@ class _ConstantEncoder(object):
         return 1
 
 
-def store_of_graphs(graphs, node_feat_name='type', n_max=None):
-    """A GraphStore of networkx graphs for the GED calls: types are the graphs' node_feat_name
-    values in sorted order (only their equality matters), n_max the largest node count unless
-    given."""
-    from .graphs import ModelGraph, NodeFeatureOneHotEncoder
-    from .packer import GraphStore
-    graphs = list(graphs)
+def _type_encoder(graphs, node_feat_name):
+    from .graphs import NodeFeatureOneHotEncoder
     if not graphs:
         raise ValueError('no graphs')
     have = [len(_attr(g, node_feat_name)) for g in graphs]
@@ -145,12 +194,41 @@ def store_of_graphs(graphs, node_feat_name='type', n_max=None):
         enc = _ConstantEncoder()
     else:
         raise ValueError('some nodes have no {!r} attribute'.format(node_feat_name))
+    return enc
+
+
+def csr_store_of_graphs(graphs, node_feat_name='type'):
+    """A web.CsrStore of networkx graphs for the GED calls, for graphs of at most 512 nodes:
+    types are encoded as store_of_graphs encodes them."""
+    from .graphs import ModelGraph
+    from .web import CsrStore
+    graphs = list(graphs)
+    enc = _type_encoder(graphs, node_feat_name)
+    nm = max(g.number_of_nodes() for g in graphs)
+    if nm > GED_CSR_MAX_NODES:
+        raise _lib.SiameseHipError('the bipartite GED bounds serve graph-store graphs of at most '
+                                   '{} nodes (largest here: {})'.format(GED_CSR_MAX_NODES, nm))
+    return CsrStore([ModelGraph(g, enc) for g in graphs], enc.input_dim())
+
+
+def store_of_graphs(graphs, node_feat_name='type', n_max=None):
+    """A GraphStore of networkx graphs for the GED calls: types are the graphs' node_feat_name
+    values in sorted order (only their equality matters), n_max the largest node count unless
+    given."""
+    from .graphs import ModelGraph
+    from .packer import GraphStore
+    graphs = list(graphs)
+    enc = _type_encoder(graphs, node_feat_name)
     nm = max(g.number_of_nodes() for g in graphs)
     n_max = max(nm, 1) if n_max is None else int(n_max)
     if n_max > GED_MAX_NODES:
         raise _lib.SiameseHipError('the bipartite GED bounds serve graphs of at most {} nodes '
                                    '(largest here: {})'.format(GED_MAX_NODES, nm))
     return GraphStore([ModelGraph(g, enc) for g in graphs], n_max, enc.input_dim())
+
+
+def _largest(graphs):
+    return max((g.number_of_nodes() for g in graphs), default=0)
 
 
 def _attr(g, name):
@@ -167,7 +245,13 @@ def ged_matrix(graphs_or_store, both_orders=True, device='cuda', node_feat_name=
     same pair from the beam search."""
     store = graphs_or_store
     if not hasattr(store, 'to_device'):
-        store = store_of_graphs(graphs_or_store, node_feat_name)
+        graphs = list(graphs_or_store)
+        # the graph-store route has the bounds only: with exact_budget or beam_width a graph of
+        # more than 32 nodes is refused by store_of_graphs, as before
+        if _largest(graphs) > GED_MAX_NODES and exact_budget is None and beam_width is None:
+            store = csr_store_of_graphs(graphs, node_feat_name)
+        else:
+            store = store_of_graphs(graphs, node_feat_name)
     if exact_budget is not None or beam_width is not None:
         ub, lb = ged_grid(store, both_orders=both_orders, bounds=True, device=device,
                           exact_budget=exact_budget, beam_width=beam_width)
@@ -181,7 +265,12 @@ def ged_pair(g1, g2, device='cuda', node_feat_name='type', exact_budget=None, be
     """(ub, lb) of two networkx graphs through a two-graph store, ub the min over both
     assignment orders; with exact_budget=B those of the budgeted search (ub == lb: proven),
     with beam_width=w those of the beam search."""
-    store = store_of_graphs([g1, g2], node_feat_name)
+    # the graph-store route has the bounds only (with exact_budget or beam_width a graph of more
+    # than 32 nodes is refused by store_of_graphs, as before)
+    if _largest([g1, g2]) > GED_MAX_NODES and exact_budget is None and beam_width is None:
+        store = csr_store_of_graphs([g1, g2], node_feat_name)
+    else:
+        store = store_of_graphs([g1, g2], node_feat_name)
     ub, lb = ged_grid(store, [0], [1], both_orders=True, bounds=True, device=device,
                       exact_budget=exact_budget, beam_width=beam_width)
     return int(ub.item()), int(lb.item())
