@@ -320,6 +320,14 @@ def lib():
         L.sg_csr_ged_grid.argtypes = [ctypes.POINTER(SgCsrStore), vp, c_i64, vp, c_i64, c_i32, vp,
                                       c_i64, vp, vp, vp, vp, vp]
         L.sg_csr_ged_grid.restype = c_i32
+    # maximum common induced subgraph under a budget (include/siamese_mcs.h); a library
+    # without it still loads
+    if all(hasattr(L, s) for s in MCS_SYMBOLS):
+        L.sg_mcs_grid_workspace_bytes.argtypes = [c_i64, c_i64, c_i32]
+        L.sg_mcs_grid_workspace_bytes.restype = c_i64
+        L.sg_mcs_grid.argtypes = [vp, vp, vp, c_i32, c_i32, vp, c_i64, vp, c_i64, c_i32, c_i64,
+                                  vp, c_i64, vp, vp, vp, vp, vp, vp, vp]
+        L.sg_mcs_grid.restype = c_i32
     _lib = L
     return L
 
@@ -405,6 +413,11 @@ GED_BEAM_MAX_WIDTH = 128
 # up to 512 nodes; detected by presence)
 GED_CSR_SYMBOLS = ('sg_csr_ged_grid_workspace_bytes', 'sg_csr_ged_grid')
 GED_CSR_MAX_NODES = 512
+
+# the symbols of include/siamese_mcs.h (maximum common induced subgraph under an expansion
+# budget: a McSplit search per pair of a dense-store grid; detected by presence)
+MCS_SYMBOLS = ('sg_mcs_grid_workspace_bytes', 'sg_mcs_grid')
+MCS_MAX_BUDGET = 1 << 24
 
 # class_start entries of sg_pair_order_cls (include/siamese_hip.h SG_FAST_CLASSES_P1)
 FAST_CLASSES_P1 = 5
@@ -899,6 +912,7 @@ _ged_fn = functools.partial(_optional_fn, header='siamese_ged.h')
 _ged_exact_fn = functools.partial(_optional_fn, header='siamese_ged_exact.h')
 _ged_beam_fn = functools.partial(_optional_fn, header='siamese_ged_beam.h')
 _ged_csr_fn = functools.partial(_optional_fn, header='siamese_ged_csr.h')
+_mcs_fn = functools.partial(_optional_fn, header='siamese_mcs.h')
 
 
 def web_embed_drop_workspace_bytes(m: SgModel, count: int) -> int:
@@ -1120,6 +1134,30 @@ def csr_ged_grid(store: SgCsrStore, q_idx, n_q, db_idx, n_db, both_orders, ub_ou
         ctypes.byref(store), _ptr(q_idx), int(n_q), _ptr(db_idx), int(n_db),
         int(bool(both_orders)), _ptr(ub_out), int(ld), _ptr(lb_out), _ptr(map_out), _ptr(status),
         _ptr(workspace), _stream(stream)), 'sg_csr_ged_grid')
+
+
+def mcs_grid_workspace_bytes(n_q: int, n_db: int, n_max: int) -> int:
+    b = int(_mcs_fn('sg_mcs_grid_workspace_bytes')(int(n_q), int(n_db), int(n_max)))
+    if b < 0:
+        raise SiameseHipError('sg_mcs_grid_workspace_bytes: the call serves stores of '
+                              '1 <= n_max <= 32 and grids of at most 2^24 rows, 2^24 columns '
+                              'and 2^32 pairs')
+    return b
+
+
+def mcs_grid(store_dev, n_max, q_idx, n_q, db_idx, n_db, connected, max_expansions, size_out, ld,
+             bound_out, edges_out=None, map_out=None, expansions_out=None, status=None,
+             workspace=None, stream=None):
+    """sg_mcs_grid over a device dense store (adj, types, n) = GraphStore.to_device(): size_out /
+    bound_out int32 [n_q] rows of stride ld (size == bound: proven), optionally the edges of the
+    incumbent's map (int32, stride ld), the map itself (int8 [n_q][n_db][n_max]) and the
+    expansions spent (int64, stride ld); q_idx / db_idx int32 device tensors or None."""
+    adj, types, n = store_dev
+    check(_mcs_fn('sg_mcs_grid')(
+        _ptr(adj), _ptr(types), _ptr(n), int(n.numel()), int(n_max), _ptr(q_idx), int(n_q),
+        _ptr(db_idx), int(n_db), int(bool(connected)), int(max_expansions), _ptr(size_out),
+        int(ld), _ptr(bound_out), _ptr(edges_out), _ptr(map_out), _ptr(expansions_out),
+        _ptr(status), _ptr(workspace), _stream(stream)), 'sg_mcs_grid')
 
 
 def seed_advance(seed_dev, delta=1, stream=None):

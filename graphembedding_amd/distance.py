@@ -9,6 +9,9 @@ bipartite upper bound (include/siamese_ged.h; include/siamese_ged_csr.h for grap
 of 33 to 512 nodes), 'exact', the budgeted branch
 and bound seeded with it (include/siamese_ged_exact.h), and 'lbeam<w>', the
 level-synchronous beam search seeded with it (include/siamese_ged_beam.h).
+`mcs` is computed on the device too (graphembedding_amd.mcs, include/siamese_mcs.h):
+the maximum common induced subgraph under type equality, which is not chorus's
+MCS-DR.
 """
 from __future__ import annotations
 
@@ -60,5 +63,17 @@ def ged(g1, g2, algo, debug=False, timeit=False):
         'Provide a cached gid-pair distance map instead.')
 
 
-def mcs(g1, g2):
-    raise RuntimeError('MCS needs the external chorus library (reference src/distance.py:10-20).')
+def mcs(g1, g2, connected=False):
+    """The node count of a maximum common induced subgraph of g1 and g2 under type equality
+    (with connected=True of a connected one), proven by the budgeted McSplit search of
+    include/siamese_mcs.h within mcs.MCS_DEFAULT_BUDGET = 2^20 expansions; a pair it cannot
+    prove raises with the size and the bound it has.  Graphs of at most 32 nodes.
+
+    It is not chorus's MCS-DR bond count (reference src/distance.py:10-20: a connected maximum
+    common edge subgraph over atom and bond labels): chorus's values are not claimed."""
+    from . import mcs as _mcs
+    size, bound, _ = _mcs.mcs_pair(g1, g2, connected=connected, budget=_mcs.MCS_DEFAULT_BUDGET)
+    if size != bound:
+        raise RuntimeError('MCS not proven within {} expansions: size {} bound {}'.format(
+            _mcs.MCS_DEFAULT_BUDGET, size, bound))
+    return size
