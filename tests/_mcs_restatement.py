@@ -44,23 +44,39 @@ class _Stop(Exception):
     pass
 
 
-def search(g1, g2, connected, budget=None):
+TRACE_KEYS = ('classes_expanded', 'classes_child', 'level', 'no_class')
+
+
+def search(g1, g2, connected, budget=None, trace=None):
     """Depth-first McSplit from the root.  Returns (proven, expansions, ub0, improvements):
     improvements is the list of (expansion number, size, phi) of every new incumbent, in order.
-    budget None: unlimited."""
+    budget None: unlimited.
+
+    trace: a dict that receives what the search reached, and changes no result: the largest class
+    count of an expanded state ('classes_expanded') and of a generated child, expanded or not
+    ('classes_child'), the deepest level expanded ('level', the root is level 0) and the number
+    of expansions that found no class to select ('no_class').  Maxima and the count accumulate
+    over the calls that share a dict."""
     (n1, _, N1), (n2, _, N2) = _masks(g1), _masks(g2)
     root = root_classes(g1, g2)
     ub0 = _rest(root)
     st = dict(exp=0, inc=0, proven=False)
     log = []
 
-    def expand(M, classes):
+    def note(key, value, add=False):
+        if trace is not None:
+            trace[key] = trace.get(key, 0) + value if add else max(trace.get(key, 0), value)
+
+    def expand(M, classes, level):
         if budget is not None and st['exp'] == budget:
             raise _Stop()
         st['exp'] += 1
+        note('classes_expanded', len(classes))
+        note('level', level)
         cand = [(max(_pc(c[0]), _pc(c[1])), i) for i, c in enumerate(classes)
                 if not (connected and M) or c[2]]
         if not cand:
+            note('no_class', 1, add=True)
             return
         i = min(cand)[1]                      # smallest max(|L|, |R|), ties to the earliest
         L, Rs, adj = classes[i]
@@ -89,13 +105,17 @@ def search(g1, g2, connected, budget=None):
                     for a, b in M2:
                         phi[a] = b
                     log.append((st['exp'], len(M2), phi))
+            note('classes_child', len(child))
             if len(M2) + _rest(child) > st['inc']:
-                expand(M2, child)
+                expand(M2, child, level + 1)
 
+    if trace is not None:
+        for key in TRACE_KEYS:
+            trace.setdefault(key, 0)
     if ub0 == 0:
         return True, 0, 0, log
     try:
-        expand([], root)
+        expand([], root, 0)
         st['proven'] = True
     except _Stop:
         pass
@@ -139,6 +159,7 @@ class McsGridReference(object):
         self.store = store
         self.graphs = {}
         self.runs = {}
+        self.trace = {}          # what all its searches reached (search's trace)
 
     def graph(self, g):
         if g not in self.graphs:
@@ -151,7 +172,7 @@ class McsGridReference(object):
         have = self.runs.get(key)
         if have is None or not (have[1][0] or have[0] is None or
                                 (budget is not None and have[0] >= budget)):
-            have = (budget, search(g1, g2, bool(connected), budget))
+            have = (budget, search(g1, g2, bool(connected), budget, trace=self.trace))
             self.runs[key] = have
         return at_budget(g1, have[1], budget)
 
