@@ -312,6 +312,14 @@ def lib():
         L.sg_ged_beam_grid.argtypes = [vp, vp, vp, c_i32, c_i32, vp, c_i64, vp, c_i64, c_i32,
                                        vp, c_i64, vp, vp, vp, vp, vp, vp]
         L.sg_ged_beam_grid.restype = c_i32
+    # 2-exchange refinement of the bipartite node maps (include/siamese_ged_refine.h); a library
+    # without it still loads
+    if all(hasattr(L, s) for s in GED_REFINE_SYMBOLS):
+        L.sg_ged_refine_grid_workspace_bytes.argtypes = [c_i64, c_i64, c_i32]
+        L.sg_ged_refine_grid_workspace_bytes.restype = c_i64
+        L.sg_ged_refine_grid.argtypes = [vp, vp, vp, c_i32, c_i32, vp, c_i64, vp, c_i64, c_i32,
+                                         vp, c_i64, vp, vp, vp, vp, vp, vp]
+        L.sg_ged_refine_grid.restype = c_i32
     # bipartite graph edit distance bounds for graph-store (CSR) graphs
     # (include/siamese_ged_csr.h); a library without them still loads
     if all(hasattr(L, s) for s in GED_CSR_SYMBOLS):
@@ -408,6 +416,11 @@ GED_EXACT_MAX_BUDGET = 1 << 24
 # presence)
 GED_BEAM_SYMBOLS = ('sg_ged_beam_grid_workspace_bytes', 'sg_ged_beam_grid')
 GED_BEAM_MAX_WIDTH = 128
+
+# the symbols of include/siamese_ged_refine.h (local search on the node map: the 2-exchange
+# refinement of both bipartite maps, for all graphs of the store; detected by presence)
+GED_REFINE_SYMBOLS = ('sg_ged_refine_grid_workspace_bytes', 'sg_ged_refine_grid')
+GED_REFINE_MAX_MOVES = 4096
 
 # the symbols of include/siamese_ged_csr.h (the bipartite bounds for graph-store (CSR) graphs of
 # up to 512 nodes; detected by presence)
@@ -911,6 +924,7 @@ _eval_fn = functools.partial(_optional_fn, header='siamese_eval.h')
 _ged_fn = functools.partial(_optional_fn, header='siamese_ged.h')
 _ged_exact_fn = functools.partial(_optional_fn, header='siamese_ged_exact.h')
 _ged_beam_fn = functools.partial(_optional_fn, header='siamese_ged_beam.h')
+_ged_refine_fn = functools.partial(_optional_fn, header='siamese_ged_refine.h')
 _ged_csr_fn = functools.partial(_optional_fn, header='siamese_ged_csr.h')
 _mcs_fn = functools.partial(_optional_fn, header='siamese_mcs.h')
 
@@ -1113,6 +1127,30 @@ def ged_beam_grid(store_dev, n_max, q_idx, n_q, db_idx, n_db, width, ub_out, ld,
         _ptr(db_idx), int(n_db), int(width), _ptr(ub_out), int(ld), _ptr(lb_out),
         _ptr(map_out), _ptr(expanded_out), _ptr(status), _ptr(workspace), _stream(stream)),
         'sg_ged_beam_grid')
+
+
+def ged_refine_grid_workspace_bytes(n_q: int, n_db: int, n_max: int) -> int:
+    b = int(_ged_refine_fn('sg_ged_refine_grid_workspace_bytes')(int(n_q), int(n_db),
+                                                                 int(n_max)))
+    if b < 0:
+        raise SiameseHipError('sg_ged_refine_grid_workspace_bytes: the call serves stores of '
+                              '1 <= n_max <= 32 and grids of at most 2^24 rows, 2^24 columns '
+                              'and 2^32 pairs')
+    return b
+
+
+def ged_refine_grid(store_dev, n_max, q_idx, n_q, db_idx, n_db, max_moves, ub_out, ld, lb_out,
+                    map_out=None, moves_out=None, status=None, workspace=None, stream=None):
+    """sg_ged_refine_grid over a device dense store (adj, types, n) = GraphStore.to_device():
+    ub_out / lb_out int32 [n_q] rows of stride ld (lb is the bipartite one), optionally the map
+    of the path that costs ub (int8 [n_q][n_db][n_max]) and the moves accepted (int32, stride
+    ld); q_idx / db_idx int32 device tensors or None."""
+    adj, types, n = store_dev
+    check(_ged_refine_fn('sg_ged_refine_grid')(
+        _ptr(adj), _ptr(types), _ptr(n), int(n.numel()), int(n_max), _ptr(q_idx), int(n_q),
+        _ptr(db_idx), int(n_db), int(max_moves), _ptr(ub_out), int(ld), _ptr(lb_out),
+        _ptr(map_out), _ptr(moves_out), _ptr(status), _ptr(workspace), _stream(stream)),
+        'sg_ged_refine_grid')
 
 
 def csr_ged_grid_workspace_bytes(n_q: int, n_db: int, n_max: int) -> int:

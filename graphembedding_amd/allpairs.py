@@ -94,12 +94,13 @@ def load_graph_set(name: str = 'syn_aids700nef', n_max: int = 10, seed: int = 12
     bound's ub at ged.GED_EXACT_DEFAULT_BUDGET expansions per pair, the exact distance wherever
     it is proven (the count of unproven pairs is logged); ged='lbeam<w>' (w in [1, 128], e.g.
     'lbeam80'): the level-synchronous beam search's ub at width w (ged.beam_label_matrix), for
-    every graph of the store."""
+    every graph of the store; ged='bpswap': the 2-exchange refinement of both bipartite maps
+    (ged.refine_label_matrix), a ub never above 'bp', for every graph of the store."""
     from .ged import beam_width_of
     beam = beam_width_of(ged)
-    if ged not in ('synthetic', 'bp', 'exact') and beam is None:
+    if ged not in ('synthetic', 'bp', 'exact', 'bpswap') and beam is None:
         raise RuntimeError('Unknown ged labels {}'.format(ged))
-    if (ged in ('bp', 'exact') or beam is not None) and not with_store:
+    if (ged in ('bp', 'exact', 'bpswap') or beam is not None) and not with_store:
         raise RuntimeError("ged={!r} computes from the dense store: with_store=True is "
                            "needed".format(ged))
     tr, te = synthetic_graphs(name, seed)
@@ -118,6 +119,9 @@ def load_graph_set(name: str = 'syn_aids700nef', n_max: int = 10, seed: int = 12
     elif beam is not None:
         from .ged import beam_label_matrix
         dmat = beam_label_matrix(store, width=beam, device=device)
+    elif ged == 'bpswap':
+        from .ged import refine_label_matrix
+        dmat = refine_label_matrix(store, device=device)
     else:
         dmat = synthetic_ged_matrix(graphs)
     return GraphSet(graphs=graphs, mgs=mgs, d_in=enc.input_dim(), n_max=n_max, store=store,

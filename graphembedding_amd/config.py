@@ -79,7 +79,9 @@ DEFAULTS: Dict[str, Any] = dict(
     # budgeted branch and bound seeded with them (ged.exact_label_matrix): the exact distance
     # wherever it is proven (graphs of at most about 10 nodes), its best ub elsewhere |
     # 'lbeam<w>' (w in [1, 128], e.g. 'lbeam80') = the level-synchronous beam search of width w
-    # seeded with them (ged.beam_label_matrix): all graphs of at most 32 nodes
+    # seeded with them (ged.beam_label_matrix): all graphs of at most 32 nodes | 'bpswap' = the
+    # 2-exchange refinement of both bipartite maps (ged.refine_label_matrix): a ub never above
+    # 'bp', all graphs of at most 32 nodes
     ged_labels='synthetic',
     n_max=None,                # record node capacity (default: Padding max_in_dims or data max)
     record_dtype='f32',        # storage of Â in pair records: 'f32' | 'bf16' (config C3); fp32 math

@@ -3,12 +3,13 @@
 Only `normalized_dist` (distance.py:59-60) is on the hot path.  `ged` and `mcs`
 shell out to the Java graph-matching-toolkit / the `chorus` library in the
 reference (distance.py:10-56); those solvers are out of scope here and raise
-unless a cached distance exists (see dist_calculator.DistCalculator).  Three
+unless a cached distance exists (see dist_calculator.DistCalculator).  Four
 algorithms are computed here, on the device (graphembedding_amd.ged): 'bp', the
 bipartite upper bound (include/siamese_ged.h; include/siamese_ged_csr.h for graphs
 of 33 to 512 nodes), 'exact', the budgeted branch
-and bound seeded with it (include/siamese_ged_exact.h), and 'lbeam<w>', the
-level-synchronous beam search seeded with it (include/siamese_ged_beam.h).
+and bound seeded with it (include/siamese_ged_exact.h), 'lbeam<w>', the
+level-synchronous beam search seeded with it (include/siamese_ged_beam.h), and
+'bpswap', the 2-exchange refinement of its maps (include/siamese_ged_refine.h).
 `mcs` is computed on the device too (graphembedding_amd.mcs, include/siamese_mcs.h):
 the maximum common induced subgraph under type equality, which is not chorus's
 MCS-DR.
@@ -40,11 +41,19 @@ def ged(g1, g2, algo, debug=False, timeit=False):
     'beam<w>': the toolkit's beam search is best-first over a truncated OPEN list, this one
     keeps the w best states of every level, so its values are not claimed to be the toolkit's.
 
+    algo='bpswap': 'bp' after local search on the node map (include/siamese_ged_refine.h): the
+    2-exchange refinement of both assignment orders' maps within ged.GED_REFINE_DEFAULT_MOVES
+    = 1024 accepted moves per start, never above 'bp', for graphs of at most 32 nodes.  The
+    name is this project's; no toolkit value is claimed.
+
     Every other algo raises: the toolkit's own A*, beam search ('beam80'), 'hungarian' and 'vj'
     are out of scope."""
     if algo == 'bp':
         from .ged import ged_pair
         return ged_pair(g1, g2)[0]
+    if algo == 'bpswap':
+        from .ged import GED_REFINE_DEFAULT_MOVES, ged_pair
+        return ged_pair(g1, g2, refine_moves=GED_REFINE_DEFAULT_MOVES)[0]
     if isinstance(algo, str) and algo.startswith('lbeam'):
         from .ged import beam_width_of, ged_pair
         w = beam_width_of(algo)

@@ -18,6 +18,11 @@ With beam_width the calls go through include/siamese_ged_beam.h: a level-synchro
 most beam_width states per pair, seeded with the same bounds, for every graph of the store (no
 16-node limit).  It tightens ub, and proves the distance (lb == ub) where the width never cut a
 level.  It is not the graph-matching-toolkit's beam search and does not claim its values.
+
+With refine_moves the calls go through include/siamese_ged_refine.h: local search on the node
+map, the 2-exchange refinement (K-REFINE with K = 2) of both bipartite maps, of at most
+refine_moves accepted moves per start, for every graph of the store.  It tightens ub and proves
+nothing by itself: lb stays the bipartite one.
 """
 from __future__ import annotations
 
@@ -30,6 +35,7 @@ GED_CSR_MAX_NODES = 512              # graph-store (CSR) graphs: the bipartite b
 GED_EXACT_MAX_NODES = 16             # larger graphs keep the bipartite bounds
 GED_EXACT_DEFAULT_BUDGET = 1 << 20   # expansions per pair of distance.ged(..., 'exact')
 GED_BEAM_DEFAULT_WIDTH = 80          # states per level of beam_label_matrix
+GED_REFINE_DEFAULT_MOVES = 1024      # accepted moves per start of refine_label_matrix
 
 
 def _index(idx, device):
@@ -41,7 +47,7 @@ def _index(idx, device):
 
 def ged_grid(store, q_idx=None, db_idx=None, both_orders=True, bounds=False, mapping=False,
              device='cuda', ld=None, return_status=False, exact_budget=None, expansions=False,
-             beam_width=None, expanded=False):
+             beam_width=None, expanded=False, refine_moves=None, moves=False):
     """Bipartite GED bounds of store graphs q_idx x db_idx (None: every graph of the store).
 
     Returns the upper bound ub as a device int32 tensor [m][n] (min over both assignment
@@ -61,28 +67,39 @@ def ged_grid(store, q_idx=None, db_idx=None, both_orders=True, bounds=False, map
     beam was never truncated, and expanded=True additionally returns the int32 tensor [m][n] of
     states expanded, in the place expansions takes.
 
+    refine_moves=k (an int in [0, 4096]; not together with exact_budget or beam_width) runs the
+    2-exchange refinement of both bipartite maps on every pair instead, at most k accepted moves
+    per start, and returns (ub, lb, ...) in the same way: lb is the bipartite one, and moves=True
+    additionally returns the int32 tensor [m][n] of moves accepted, in the place expanded takes.
+
     A graph store (web.CsrStore) goes through sg_csr_ged_grid: the same bounds for graphs of at
-    most 512 nodes, the mapping an int16 tensor; exact_budget and beam_width raise ValueError
-    there."""
+    most 512 nodes, the mapping an int16 tensor; exact_budget, beam_width and refine_moves raise
+    ValueError there."""
     import torch
     if _is_csr(store):
-        if exact_budget is not None or beam_width is not None or expansions or expanded:
+        if (exact_budget is not None or beam_width is not None or refine_moves is not None
+                or expansions or expanded or moves):
             raise ValueError('a graph store (CSR) has the bipartite bounds only: no exact_budget, '
-                             'no beam_width')
+                             'no beam_width, no refine_moves')
         return _csr_ged_grid(store, q_idx, db_idx, both_orders, bounds, mapping, device, ld,
                              return_status)
     exact = exact_budget is not None
     beam = beam_width is not None
-    if exact and beam:
-        raise ValueError('exact_budget and beam_width are mutually exclusive')
+    refine = refine_moves is not None
+    if exact + beam + refine > 1:
+        raise ValueError('exact_budget, beam_width and refine_moves are mutually exclusive')
     if expansions and not exact:
         raise ValueError('expansions are counted by the exact search: pass exact_budget')
     if expanded and not beam:
         raise ValueError('expanded states are counted by the beam search: pass beam_width')
+    if moves and not refine:
+        raise ValueError('moves are counted by the refinement: pass refine_moves')
     if exact and not both_orders:
         raise ValueError('the exact search is seeded with both assignment orders')
     if beam and not both_orders:
         raise ValueError('the beam search is seeded with both assignment orders')
+    if refine and not both_orders:
+        raise ValueError('the refinement starts from both assignment orders')
     adj, types, n_nodes = store.to_device(device)
     G = int(n_nodes.numel())
     dev = adj.device
@@ -94,13 +111,14 @@ def ged_grid(store, q_idx=None, db_idx=None, both_orders=True, bounds=False, map
         raise ValueError('ld {} below n {}'.format(ld, n))
     nbytes = (_lib.ged_exact_grid_workspace_bytes if exact else
               _lib.ged_beam_grid_workspace_bytes if beam else
+              _lib.ged_refine_grid_workspace_bytes if refine else
               _lib.ged_grid_workspace_bytes)(m, n, store.n_max)
     ws = torch.empty(nbytes // 4 + 1, dtype=torch.int32, device=dev)
     ub = torch.empty((m, ld), dtype=torch.int32, device=dev)
-    lb = torch.empty((m, ld), dtype=torch.int32, device=dev) if bounds or exact or beam else None
+    lb = torch.empty((m, ld), dtype=torch.int32, device=dev) if bounds or exact or beam or refine else None
     mp = torch.empty((m, n, store.n_max), dtype=torch.int8, device=dev) if mapping else None
     ex = torch.empty((m, ld), dtype=torch.int64, device=dev) if expansions else None
-    if expanded:
+    if expanded or moves:
         ex = torch.empty((m, ld), dtype=torch.int32, device=dev)
     status = torch.zeros(1, dtype=torch.int32, device=dev)
     if exact:
@@ -109,6 +127,9 @@ def ged_grid(store, q_idx=None, db_idx=None, both_orders=True, bounds=False, map
     elif beam:
         _lib.ged_beam_grid((adj, types, n_nodes), store.n_max, q, m, db, n, int(beam_width),
                            ub, ld, lb, mp, ex, status, ws)
+    elif refine:
+        _lib.ged_refine_grid((adj, types, n_nodes), store.n_max, q, m, db, n, int(refine_moves),
+                             ub, ld, lb, mp, ex, status, ws)
     else:
         _lib.ged_grid((adj, types, n_nodes), store.n_max, q, m, db, n, both_orders, ub, ld, lb,
                       mp, status, ws)
@@ -118,14 +139,15 @@ def ged_grid(store, q_idx=None, db_idx=None, both_orders=True, bounds=False, map
             raise _lib.SiameseHipError('{}: {} (a graph id outside the store, or a '
                                        'node count outside [1, n_max])'.format(
                                            'sg_ged_exact_grid' if exact else
-                                           'sg_ged_beam_grid' if beam else 'sg_ged_grid',
+                                           'sg_ged_beam_grid' if beam else
+                                           'sg_ged_refine_grid' if refine else 'sg_ged_grid',
                                            _lib._ERR_NAMES.get(rc, rc)))
     out = [ub[:, :n]]
     if bounds:
         out.append(lb[:, :n])
     if mapping:
         out.append(mp)
-    if expansions or expanded:
+    if expansions or expanded or moves:
         out.append(ex[:, :n])
     if return_status:
         out.append(status)
@@ -237,42 +259,49 @@ def _attr(g, name):
 
 
 def ged_matrix(graphs_or_store, both_orders=True, device='cuda', node_feat_name='type',
-               exact_budget=None, beam_width=None):
+               exact_budget=None, beam_width=None, refine_moves=None):
     """All-pairs upper bounds as a host int64 matrix [G][G], ready for
     DistCalculator.from_matrix.  With both_orders it is symmetric with a zero diagonal.
     With exact_budget=B: (matrix, proven), the budgeted search's ub and the bool matrix of the
     pairs whose distance it proved (ub is the exact distance there); with beam_width=w the
-    same pair from the beam search."""
+    same pair from the beam search, with refine_moves=k from the 2-exchange refinement (proven
+    there: the refined ub meets the bipartite lb)."""
     store = graphs_or_store
     if not hasattr(store, 'to_device'):
         graphs = list(graphs_or_store)
-        # the graph-store route has the bounds only: with exact_budget or beam_width a graph of
-        # more than 32 nodes is refused by store_of_graphs, as before
-        if _largest(graphs) > GED_MAX_NODES and exact_budget is None and beam_width is None:
+        # the graph-store route has the bounds only: with exact_budget, beam_width or
+        # refine_moves a graph of more than 32 nodes is refused by store_of_graphs, as before
+        if _largest(graphs) > GED_MAX_NODES and exact_budget is None and beam_width is None \
+                and refine_moves is None:
             store = csr_store_of_graphs(graphs, node_feat_name)
         else:
             store = store_of_graphs(graphs, node_feat_name)
-    if exact_budget is not None or beam_width is not None:
+    if exact_budget is not None or beam_width is not None or refine_moves is not None:
         ub, lb = ged_grid(store, both_orders=both_orders, bounds=True, device=device,
-                          exact_budget=exact_budget, beam_width=beam_width)
+                          exact_budget=exact_budget, beam_width=beam_width,
+                          refine_moves=refine_moves)
         ub, lb = ub.cpu().numpy().astype(np.int64), lb.cpu().numpy().astype(np.int64)
         return ub, ub == lb
     ub = ged_grid(store, both_orders=both_orders, device=device)
     return ub.cpu().numpy().astype(np.int64)
 
 
-def ged_pair(g1, g2, device='cuda', node_feat_name='type', exact_budget=None, beam_width=None):
+def ged_pair(g1, g2, device='cuda', node_feat_name='type', exact_budget=None, beam_width=None,
+             refine_moves=None):
     """(ub, lb) of two networkx graphs through a two-graph store, ub the min over both
     assignment orders; with exact_budget=B those of the budgeted search (ub == lb: proven),
-    with beam_width=w those of the beam search."""
-    # the graph-store route has the bounds only (with exact_budget or beam_width a graph of more
-    # than 32 nodes is refused by store_of_graphs, as before)
-    if _largest([g1, g2]) > GED_MAX_NODES and exact_budget is None and beam_width is None:
+    with beam_width=w those of the beam search, with refine_moves=k those of the 2-exchange
+    refinement."""
+    # the graph-store route has the bounds only (with exact_budget, beam_width or refine_moves a
+    # graph of more than 32 nodes is refused by store_of_graphs, as before)
+    if _largest([g1, g2]) > GED_MAX_NODES and exact_budget is None and beam_width is None \
+            and refine_moves is None:
         store = csr_store_of_graphs([g1, g2], node_feat_name)
     else:
         store = store_of_graphs([g1, g2], node_feat_name)
     ub, lb = ged_grid(store, [0], [1], both_orders=True, bounds=True, device=device,
-                      exact_budget=exact_budget, beam_width=beam_width)
+                      exact_budget=exact_budget, beam_width=beam_width,
+                      refine_moves=refine_moves)
     return int(ub.item()), int(lb.item())
 
 
@@ -300,6 +329,19 @@ def beam_label_matrix(graphs_or_store, width=GED_BEAM_DEFAULT_WIDTH, device='cud
     logging.getLogger(__name__).info(
         'beam GED labels: %d of %d pairs left unproven at width %d',
         int((~proven).sum()), proven.size, width)
+    return dmat
+
+
+def refine_label_matrix(graphs_or_store, moves=GED_REFINE_DEFAULT_MOVES, device='cuda',
+                        node_feat_name='type'):
+    """The label matrix of ged='bpswap' / ged_labels='bpswap': the refined bipartite ub for all
+    pairs, with the number of pairs left unproven logged (their ub is the best path found)."""
+    import logging
+    dmat, proven = ged_matrix(graphs_or_store, device=device, node_feat_name=node_feat_name,
+                              refine_moves=moves)
+    logging.getLogger(__name__).info(
+        'refined GED labels: %d of %d pairs left unproven within %d moves per start',
+        int((~proven).sum()), proven.size, moves)
     return dmat
 
 

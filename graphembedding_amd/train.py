@@ -199,6 +199,9 @@ def main(flags=None, device='cuda', return_objects=False):
         elif f.ged_labels == 'exact':   # the budgeted exact search; ub where unproven
             from .ged import exact_label_matrix
             dmat = exact_label_matrix(gs, device=device, node_feat_name=f.node_feat_name)
+        elif f.ged_labels == 'bpswap':   # the 2-exchange refinement of both bipartite maps
+            from .ged import refine_label_matrix
+            dmat = refine_label_matrix(gs, device=device, node_feat_name=f.node_feat_name)
         elif f.ged_labels == 'synthetic':
             dmat = synthetic_ged_matrix(gs)
         else:
