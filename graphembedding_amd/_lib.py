@@ -320,6 +320,14 @@ def lib():
         L.sg_ged_refine_grid.argtypes = [vp, vp, vp, c_i32, c_i32, vp, c_i64, vp, c_i64, c_i32,
                                          vp, c_i64, vp, vp, vp, vp, vp, vp]
         L.sg_ged_refine_grid.restype = c_i32
+    # k nearest graphs under exact graph edit distance (include/siamese_ged_knn.h); a library
+    # without it still loads
+    if all(hasattr(L, s) for s in GED_KNN_SYMBOLS):
+        L.sg_ged_knn_workspace_bytes.argtypes = [c_i64, c_i64, c_i32, c_i32]
+        L.sg_ged_knn_workspace_bytes.restype = c_i64
+        L.sg_ged_knn.argtypes = [vp, vp, vp, c_i32, c_i32, vp, c_i64, vp, c_i64, c_i32, c_i64,
+                                 vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.sg_ged_knn.restype = c_i32
     # bipartite graph edit distance bounds for graph-store (CSR) graphs
     # (include/siamese_ged_csr.h); a library without them still loads
     if all(hasattr(L, s) for s in GED_CSR_SYMBOLS):
@@ -421,6 +429,11 @@ GED_BEAM_MAX_WIDTH = 128
 # refinement of both bipartite maps, for all graphs of the store; detected by presence)
 GED_REFINE_SYMBOLS = ('sg_ged_refine_grid_workspace_bytes', 'sg_ged_refine_grid')
 GED_REFINE_MAX_MOVES = 4096
+
+# the symbols of include/siamese_ged_knn.h (the k nearest graphs under exact graph edit
+# distance: filter by the bipartite bounds, verify under a cutoff)
+GED_KNN_SYMBOLS = ('sg_ged_knn_workspace_bytes', 'sg_ged_knn')
+GED_KNN_MAX_K = 64
 
 # the symbols of include/siamese_ged_csr.h (the bipartite bounds for graph-store (CSR) graphs of
 # up to 512 nodes; detected by presence)
@@ -926,6 +939,7 @@ _ged_exact_fn = functools.partial(_optional_fn, header='siamese_ged_exact.h')
 _ged_beam_fn = functools.partial(_optional_fn, header='siamese_ged_beam.h')
 _ged_refine_fn = functools.partial(_optional_fn, header='siamese_ged_refine.h')
 _ged_csr_fn = functools.partial(_optional_fn, header='siamese_ged_csr.h')
+_ged_knn_fn = functools.partial(_optional_fn, header='siamese_ged_knn.h')
 _mcs_fn = functools.partial(_optional_fn, header='siamese_mcs.h')
 
 
@@ -1151,6 +1165,30 @@ def ged_refine_grid(store_dev, n_max, q_idx, n_q, db_idx, n_db, max_moves, ub_ou
         _ptr(db_idx), int(n_db), int(max_moves), _ptr(ub_out), int(ld), _ptr(lb_out),
         _ptr(map_out), _ptr(moves_out), _ptr(status), _ptr(workspace), _stream(stream)),
         'sg_ged_refine_grid')
+
+
+def ged_knn_workspace_bytes(n_q: int, n_db: int, n_max: int, k: int) -> int:
+    b = int(_ged_knn_fn('sg_ged_knn_workspace_bytes')(int(n_q), int(n_db), int(n_max), int(k)))
+    if b < 0:
+        raise SiameseHipError('sg_ged_knn_workspace_bytes: the call serves stores of '
+                              '1 <= n_max <= 32, grids of at most 2^24 rows, 2^24 columns '
+                              'and 2^32 pairs, and 1 <= k <= 64')
+    return b
+
+
+def ged_knn(store_dev, n_max, q_idx, n_q, db_idx, n_db, k, max_expansions, col_out, ub_out,
+            lb_out, certified_out, candidates_out=None, expansions_out=None, status=None,
+            workspace=None, stream=None):
+    """sg_ged_knn over a device dense store (adj, types, n) = GraphStore.to_device(): col_out /
+    ub_out / lb_out int32 [n_q][k], certified_out int32 [n_q], optionally the candidates
+    (int32 [n_q]) and the expansions (int64 [n_q]) of every row; q_idx / db_idx int32 device
+    tensors or None; the workspace is 8-byte aligned."""
+    adj, types, n = store_dev
+    check(_ged_knn_fn('sg_ged_knn')(
+        _ptr(adj), _ptr(types), _ptr(n), int(n.numel()), int(n_max), _ptr(q_idx), int(n_q),
+        _ptr(db_idx), int(n_db), int(k), int(max_expansions), _ptr(col_out), _ptr(ub_out),
+        _ptr(lb_out), _ptr(certified_out), _ptr(candidates_out), _ptr(expansions_out),
+        _ptr(status), _ptr(workspace), _stream(stream)), 'sg_ged_knn')
 
 
 def csr_ged_grid_workspace_bytes(n_q: int, n_db: int, n_max: int) -> int:

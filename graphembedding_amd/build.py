@@ -12,10 +12,11 @@ SOURCES = ['siamese_hip.hip', 'sg_generic.hip', 'sg_fast.hip', 'sg_fast_att.hip'
            'sg_sampler.hip', 'sg_web.hip', 'sg_embed.hip', 'sg_embed_train.hip', 'sg_search.hip',
            'sg_embed_nodes.hip', 'sg_web_grid.hip', 'sg_web_search.hip', 'sg_web_train.hip',
            'sg_eval.hip', 'sg_dot_grid.hip', 'sg_ged.hip', 'sg_ged_exact.hip',
-           'sg_ged_beam.hip', 'sg_ged_csr.hip', 'sg_mcs.hip', 'sg_ged_refine.hip']
+           'sg_ged_beam.hip', 'sg_ged_csr.hip', 'sg_mcs.hip', 'sg_ged_refine.hip',
+           'sg_ged_knn.hip']
 HEADERS = ['sg_common.h', 'sg_plan.h', 'sg_paths.h', 'sg_mfma.h', 'sg_gen_nodes.h',
            'sg_embed_plan.h', 'sg_embed_bwd.h', 'sg_web_grid.h', 'sg_search_lists.h',
-           'sg_search_split.h', 'sg_ged_common.h']
+           'sg_search_split.h', 'sg_ged_common.h', 'sg_ged_search.h']
 # MI355X only: the kernels use gfx950's 160 KB LDS (web_wgrad_kernel_b3 holds ≈66.6 KB),
 # its MFMA shapes and wave64 layouts; there is no other target
 ARCH = 'gfx950'
@@ -58,6 +59,7 @@ def _stale() -> bool:
     deps.append(os.path.join(os.path.dirname(_HERE), 'include', 'siamese_ged_csr.h'))
     deps.append(os.path.join(os.path.dirname(_HERE), 'include', 'siamese_mcs.h'))
     deps.append(os.path.join(os.path.dirname(_HERE), 'include', 'siamese_ged_refine.h'))
+    deps.append(os.path.join(os.path.dirname(_HERE), 'include', 'siamese_ged_knn.h'))
     deps.append(os.path.abspath(__file__))
     return any(os.path.isfile(d) and os.path.getmtime(d) > t for d in deps)
 

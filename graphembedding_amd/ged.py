@@ -23,6 +23,14 @@ With refine_moves the calls go through include/siamese_ged_refine.h: local searc
 map, the 2-exchange refinement (K-REFINE with K = 2) of both bipartite maps, of at most
 refine_moves accepted moves per start, for every graph of the store.  It tightens ub and proves
 nothing by itself: lb stays the bipartite one.
+
+ged_knn is the query on top of the bounds and the exact search (include/siamese_ged_knn.h): the
+k nearest database graphs of every query under exact GED, by filter and verify.  The k-th
+smallest upper bound of a row is its threshold; a pair whose lower bound exceeds it is never
+searched, and every other pair is searched from the threshold instead of its own upper bound, so
+a pair that only has to be shown farther than the threshold is cut off early.  A certified row
+is the true top-k in ascending (distance, column); knn_recall scores any other top-k (a learned
+index's `nearest`) against it.
 """
 from __future__ import annotations
 
@@ -152,6 +160,103 @@ def ged_grid(store, q_idx=None, db_idx=None, both_orders=True, bounds=False, map
     if return_status:
         out.append(status)
     return out[0] if len(out) == 1 else tuple(out)
+
+
+def ged_knn(store, q_idx=None, db_idx=None, k=10, exact_budget=GED_EXACT_DEFAULT_BUDGET,
+            device='cuda', stats=False, return_status=False):
+    """The k nearest graphs db_idx of every query q_idx of a dense store under exact GED (None:
+    every graph of the store), by sg_ged_knn: filter by the bipartite bounds, verify under the
+    row's threshold with at most exact_budget expansions per pair.
+
+    Returns (cols, ub, lb, certified) as device int32 tensors: cols [m][k] the columns (indices
+    into db_idx) in ascending (ub, column), ub / lb [m][k] their bounds (lb == ub: proven),
+    certified [m] 1 where the row is proven to be the true top-k of the exact distances in
+    ascending (distance, column).  With fewer than k servable database graphs the last slots
+    read -1.  stats=True additionally returns candidates (int32 [m], the pairs that survived
+    the filter) and expansions (int64 [m], summed over the row).  A graph id outside the store
+    or a node count outside [1, n_max] raises, unless return_status=True: then the int32 device
+    status tensor [1] is returned last, such a query's row reads -1 with certified 0 and such a
+    database graph takes no part.  A graph store (web.CsrStore) raises ValueError."""
+    import torch
+    if _is_csr(store):
+        raise ValueError('a graph store (CSR) has the bipartite bounds only: no ged_knn')
+    k = int(k)
+    if not 1 <= k <= _lib.GED_KNN_MAX_K:
+        raise ValueError('k {} outside [1, {}]'.format(k, _lib.GED_KNN_MAX_K))
+    budget = int(exact_budget)
+    if not 0 <= budget <= _lib.GED_EXACT_MAX_BUDGET:
+        raise ValueError('exact_budget {} outside [0, {}]'.format(
+            budget, _lib.GED_EXACT_MAX_BUDGET))
+    adj, types, n_nodes = store.to_device(device)
+    G = int(n_nodes.numel())
+    dev = adj.device
+    q, db = _index(q_idx, dev), _index(db_idx, dev)
+    m = G if q is None else int(q.numel())
+    n = G if db is None else int(db.numel())
+    nbytes = _lib.ged_knn_workspace_bytes(m, n, store.n_max, k)
+    ws = torch.empty(nbytes // 8 + 1, dtype=torch.int64, device=dev)   # 8-byte aligned
+    cols = torch.empty((m, k), dtype=torch.int32, device=dev)
+    ub = torch.empty((m, k), dtype=torch.int32, device=dev)
+    lb = torch.empty((m, k), dtype=torch.int32, device=dev)
+    cert = torch.empty((m,), dtype=torch.int32, device=dev)
+    cand = torch.empty((m,), dtype=torch.int32, device=dev) if stats else None
+    ex = torch.empty((m,), dtype=torch.int64, device=dev) if stats else None
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    _lib.ged_knn((adj, types, n_nodes), store.n_max, q, m, db, n, k, budget, cols, ub, lb, cert,
+                 cand, ex, status, ws)
+    if not return_status:
+        rc = int(status.item())
+        if rc != 0:
+            raise _lib.SiameseHipError('sg_ged_knn: {} (a graph id outside the store, or a '
+                                       'node count outside [1, n_max])'.format(
+                                           _lib._ERR_NAMES.get(rc, rc)))
+    out = [cols, ub, lb, cert]
+    if stats:
+        out += [cand, ex]
+    if return_status:
+        out.append(status)
+    return tuple(out)
+
+
+def ged_knn_graphs(graphs, queries, k=10, exact_budget=GED_EXACT_DEFAULT_BUDGET, device='cuda',
+                   node_feat_name='type'):
+    """ged_knn for networkx graphs, in the manner of ged_matrix: the k nearest of `graphs` for
+    every graph of `queries` as host arrays (cols int64 [m][k] indices into graphs, dist int64
+    [m][k] the ub, proven bool [m][k], certified bool [m]).  Both lists go into one store, so
+    their types are encoded together; graphs of at most 32 nodes."""
+    graphs, queries = list(graphs), list(queries)
+    store = store_of_graphs(graphs + queries, node_feat_name)
+    n = len(graphs)
+    cols, ub, lb, cert = ged_knn(store, np.arange(n, n + len(queries)), np.arange(n), k=k,
+                                 exact_budget=exact_budget, device=device)
+    ub, lb = ub.cpu().numpy().astype(np.int64), lb.cpu().numpy().astype(np.int64)
+    return cols.cpu().numpy().astype(np.int64), ub, (ub == lb) & (ub >= 0), \
+        cert.cpu().numpy().astype(bool)
+
+
+def knn_recall(pred_cols, true_cols, certified):
+    """(recall, rows): the mean over the certified rows of |pred ∩ true| / k', k' the number of
+    entries >= 0 of the row of true_cols (ged_knn's cols), and the number of rows counted.
+    pred_cols is any [m][k_pred] top-k of the same queries against the same database (entries
+    < 0 are ignored), e.g. EmbeddingIndex.nearest's; rows that are not certified or have no
+    true neighbour are left out, and with no row counted the recall is nan."""
+    pred = _host(pred_cols)
+    true = _host(true_cols)
+    cert = _host(certified).astype(bool).reshape(-1)
+    if pred.ndim != 2 or true.ndim != 2 or not pred.shape[0] == true.shape[0] == cert.shape[0]:
+        raise ValueError('pred_cols [m][k_pred], true_cols [m][k] and certified [m] of the same m')
+    total, rows = 0.0, 0
+    for p, t, c in zip(pred, true, cert):
+        want = set(int(x) for x in t if x >= 0)
+        if not c or not want:
+            continue
+        total += len(want & set(int(x) for x in p if x >= 0)) / len(want)
+        rows += 1
+    return (total / rows if rows else float('nan')), rows
+
+
+def _host(x):
+    return x.detach().cpu().numpy() if hasattr(x, 'detach') else np.asarray(x)
 
 
 def _is_csr(store):
